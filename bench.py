@@ -9,7 +9,12 @@ buffers) are resident in HBM before timing starts.  With N ranks the image tiles
 work fixed: "strong" scaling) and the film tiles are reduced to rank 0 inside the timed job;
 value = all paths of the job / max-over-ranks wall time.
 
-Also reported:
+A plain run sets up, warms up, times the steps and prints the result line: the headline figure, its
+`ms_per_step`, and the §8d pipeline figure, which comes from the timed job's own counters.  --dump-outputs DIR
+also writes the film the last timed job returned (DIR/film_rgbw.npy, DIR/film_sumsq.npy, float32): the job's
+inputs are the same in every run with the same arguments, so two builds can be compared array for array.
+
+With --full (each part takes runs of its own after the timed region), also reported:
   roofline   the dominant kernel's algorithmic bytes per launch (SURVEY.md §8d's 420 B per segment,
              split per kernel) over its average launch on a one-lane calibration context
              (the timed job overlaps three lanes): the headline `frac` with the duration from the
@@ -24,7 +29,8 @@ Also reported:
              full 31-spp training (its own records, splat and refit) and the 1024-spp final render
              of a block of tiles; with the GPU/CPU relative-RMSE ratio on those tiles.
 
-  python bench.py [--gpus N --steps K --warmup W] [--spp 1024] [--no-cpu] [--no-quality] [--quick]
+  python bench.py [--gpus N --steps K --warmup W] [--spp 1024] [--dump-outputs DIR] [--quick]
+  python bench.py --full [--no-cpu] [--no-quality]   # + roofline, quality, CPU baseline
   python bench.py --scene smoke      # C5: the guided volumetric job on the 256^3 smoke cloud at 1024^2
 """
 import argparse
@@ -69,15 +75,22 @@ def parse():
     ap.add_argument("--gpus", type=int, default=None,
                     help="ranks (one per GPU).  Without a torchrun environment and N > 1, bench.py launches N "
                          "ranks itself (torch.distributed.run, 127.0.0.1); under torchrun N must equal WORLD_SIZE")
-    ap.add_argument("--steps", type=int, default=3)
-    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 3; 1 with --quick)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed steps before them (default 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the kernel roofline (a calibration context), the image "
+                         "quality against the committed ground truth (unguided renders) and the CPU baseline (the "
+                         "oracle); --no-quality / --no-cpu leave one of them out")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the film the last timed step returned as DIR/film_rgbw.npy and DIR/film_sumsq.npy "
+                         "(float32; above 64 MB in all a fixed, seeded sample of the pixels)")
     ap.add_argument("--scene", default="ajar_door")
     ap.add_argument("--width", type=int, default=None, help="default 1280 (C3), 1024 (C5 smoke)")
     ap.add_argument("--height", type=int, default=None, help="default 720 (C3), 1024 (C5 smoke)")
     ap.add_argument("--spp", type=int, default=1024)
     ap.add_argument("--train", type=int, default=5)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-quality", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-quality", action="store_true", help="with --full: no quality block")
     ap.add_argument("--lanes", type=int, default=0, help="path chunks in flight (pg_config.path_lanes, 0 = 3)")
     ap.add_argument("--paths-in-flight", type=int, default=0, help="paths per chunk (0 = auto: C3's final render on one GPU in 12 chunks, else 2^25)")
     ap.add_argument("--exchange", default=None, choices=["allreduce", "allgather", "capi", "capi-allgather"],
@@ -87,7 +100,8 @@ def parse():
                          "PG_DIST_BACKEND=gloo, whose ranks may share a GPU, which RCCL refuses) or 'allgather'")
     ap.add_argument("--plumbing-check", action="store_true",
                     help="launcher self-test: every rank joins the process group and reports (rank, world); no GPU")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU budget of the final-render sample")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0,
+                    help="with --full: CPU budget of the final-render sample")
     ap.add_argument("--quick", action="store_true", help="small smoke configuration (not a bench line)")
     ap.add_argument("--props", default=None,
                     help="integrator properties (JSON); default: the guided configuration DESIGN.md §8a measured best "
@@ -180,7 +194,13 @@ def main():
     if a.height is None:
         a.height = 1024 if vol else 720
     if a.quick:
-        a.width, a.height, a.spp, a.steps, a.warmup = 320, 180, 64, 1, 1
+        a.width, a.height, a.spp = 320, 180, 64
+    if a.steps is None:
+        a.steps = 1 if a.quick else 3
+    if a.warmup is None:
+        a.warmup = 1
+    if a.steps < 1:
+        sys.exit("bench.py: --steps must be at least 1")
     import pgload
     pg = pgload.load()
     from mitsuba_path_guiding_amd import distributed as D
@@ -247,10 +267,10 @@ def main():
         rgbw, sq = integ.render(a.spp)
         if capi_comm:  # RCCL reduce of the device films inside the library, then rank 0 reads it
             dev.comm_reduce_film(0)
-            rgbw = dev.read_film()[0]
+            rgbw, sq = dev.read_film()
         elif world > 1:  # gather the disjoint film tiles on rank 0
             rgbw, sq = D.reduce_film(rgbw, sq, on_dev)
-        return rgbw
+        return rgbw, sq
 
     for w in range(a.warmup):
         if wd is not None and w == 0:  # kernel loading and the first pg_comm collectives
@@ -264,12 +284,14 @@ def main():
     s0 = dev.stats()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        final = job()
+        final, final_sq = job()
     barrier()
     elapsed = time.perf_counter() - t0
     s1 = dev.stats()
     if world > 1:
         elapsed = D.max_over_ranks(elapsed, on_dev)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"film_rgbw": final, "film_sumsq": final_sq})
     paths_per_job = (2 ** a.train - 1 + a.spp) * a.width * a.height
     total_paths = paths_per_job * a.steps
     value = total_paths / elapsed / 1e6
@@ -289,7 +311,7 @@ def main():
                     "algorithmic_bytes_per_step": int(pipe_bytes / a.steps),
                     "note": "density-grid gathers plus the wavefront stages' path-state bytes (bytes_model) over "
                             "the timed wall clock, all ranks"}
-        roofline = volume_roofline(d, pg, scene, integ, device, a)
+        roofline = volume_roofline(d, pg, scene, integ, device, a) if a.full else None
     else:
         # §8d's 420 B per segment, split by what each segment does: every segment is traced, escaped
         # ones are not shaded, only recording passes write training records, and only NEE vertices
@@ -302,15 +324,15 @@ def main():
                     "algorithmic_bytes_per_step": int(pipe_bytes / a.steps),
                     "note": "SURVEY.md §8d over the timed wall clock, all ranks: segments x 48 B (trace) + shaded "
                             "segments x 300 B + training records x 40 B + shadow rays x 32 B"}
-        roofline = kernel_roofline(pg, scene, integ, device, a)
+        roofline = kernel_roofline(pg, scene, integ, device, a) if a.full else None
 
     quality = None
-    if rank == 0 and world == 1 and not vol and not a.no_quality:
+    if a.full and rank == 0 and world == 1 and not vol and not a.no_quality:
         quality = quality_block(pg, scene, final, elapsed / a.steps, a)
     # ---- CPU baseline (oracle, rank 0, N = 1, bounded sample of the same guided job)
     cpu = None
     rmse = None
-    if rank == 0 and world == 1 and not a.no_cpu:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu:
         cpu, rmse = cpu_baseline(pg, scene, integ, final, a)
 
     if rank == 0:
@@ -318,7 +340,7 @@ def main():
             "metric": "Mpaths/sec + equal-spp RMSE vs CPU ref, ajar-door scene at 1/2/4/8 GPUs",
             "value": round(value, 3), "unit": "Mpaths/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
             "ms_per_step": round(elapsed / a.steps * 1e3, 3), "higher_is_better": True, "scaling": "strong",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": a.full,
             "config": {"workload": f"{'C5' if vol else 'C3'} {a.scene} {a.width}x{a.height}, guided SD-tree"
                                    f"{' volpath (phase MIS + guided free flight)' if vol else ''}, {a.train} training "
                                    f"iterations (1..{2 ** (a.train - 1)} spp) + {a.spp} spp render",
@@ -345,6 +367,20 @@ def main():
 # C3's guided configuration: the BSDF-sampling fraction bounded below by the BSDF's
 # albedo, and the glossy prior (BSDF::getGlossySamplingRate) -- rough metals and glass are not guided
 BENCH_GUIDING = {"bsdfSamplingFractionBound": "albedo", "glossyPrior": True}
+
+
+def dump_outputs(path, arrays, limit=60_000_000):
+    """--dump-outputs: each array as path/<name>.npy in float32, `limit` bytes in all.  An array over its share is
+    cut to a fixed sample of its pixels (rows of the last axis; the same seeded choice in every run, in pixel order)."""
+    os.makedirs(path, exist_ok=True)
+    share = limit // len(arrays)
+    for name, x in arrays.items():
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.nbytes > share:
+            pixels = x.reshape(-1, x.shape[-1])
+            keep = np.random.default_rng(4242).choice(len(pixels), share // (4 * x.shape[-1]), replace=False)
+            x = pixels[np.sort(keep)]
+        np.save(os.path.join(path, name + ".npy"), x)
 
 
 def kernel_roofline(pg, scene, integ, local, a, spp=32):

@@ -4,8 +4,8 @@ set -eo pipefail
 OUT=$1; A=$2; B=$3; shift 3
 mkdir -p "$OUT"
 for i in 1 2; do
-  PG_LIB=$A timeout -k 10 240 python bench.py --no-cpu --no-quality "$@" > "$OUT/a_$i.log" 2>&1
-  PG_LIB=$B timeout -k 10 240 python bench.py --no-cpu --no-quality "$@" > "$OUT/b_$i.log" 2>&1
+  PG_LIB=$A timeout -k 10 240 python bench.py --full --no-cpu --no-quality "$@" > "$OUT/a_$i.log" 2>&1
+  PG_LIB=$B timeout -k 10 240 python bench.py --full --no-cpu --no-quality "$@" > "$OUT/b_$i.log" 2>&1
 done
 python - "$OUT" <<'PY'
 import json, sys, glob, os

@@ -4,11 +4,11 @@ set -eo pipefail
 OUT=$1; A=$2; B=$3
 mkdir -p "$OUT"
 for i in 1 2; do
-  PG_LIB=$A timeout -k 10 200 python bench.py --scene smoke --steps 2 --warmup 1 --no-cpu > "$OUT/a_$i.log" 2>&1
-  PG_LIB=$B timeout -k 10 200 python bench.py --scene smoke --steps 2 --warmup 1 --no-cpu > "$OUT/b_$i.log" 2>&1
+  PG_LIB=$A timeout -k 10 200 python bench.py --scene smoke --steps 2 --warmup 1 --full --no-cpu >"$OUT/a_$i.log" 2>&1
+  PG_LIB=$B timeout -k 10 200 python bench.py --scene smoke --steps 2 --warmup 1 --full --no-cpu >"$OUT/b_$i.log" 2>&1
 done
 export TMPDIR=/tmp
-PG_LIB=$B timeout -s KILL 200 rocprofv3 --pmc FETCH_SIZE -d "$OUT/fetch_b" -o run --output-format csv -- python3 bench.py --scene smoke --steps 1 --warmup 0 --no-cpu > "$OUT/fetch_b.log" 2>&1
+PG_LIB=$B timeout -s KILL 200 rocprofv3 --pmc FETCH_SIZE -d "$OUT/fetch_b" -o run --output-format csv -- python3 bench.py --scene smoke --steps 1 --warmup 0 --full --no-cpu >"$OUT/fetch_b.log" 2>&1
 python - "$OUT" <<'PY'
 import json, sys, glob, os, csv, collections
 for f in sorted(glob.glob(os.path.join(sys.argv[1], "?_?.log"))):

@@ -8,7 +8,7 @@ while [ $# -gt 0 ] && [ "$1" != "--" ]; do LIBS+=("$1"); shift; done
 mkdir -p "$OUT"
 for i in $(seq 1 "$ROUNDS"); do
   for k in "${!LIBS[@]}"; do
-    PG_LIB=${LIBS[$k]} timeout -k 10 240 python bench.py --no-cpu --no-quality "$@" > "$OUT/v${k}_$i.log" 2>&1
+    PG_LIB=${LIBS[$k]} timeout -k 10 240 python bench.py --full --no-cpu --no-quality "$@" > "$OUT/v${k}_$i.log" 2>&1
   done
 done
 python - "$OUT" "${LIBS[@]}" <<'PY'

@@ -11,7 +11,7 @@ export TMPDIR=/tmp
 run() {  # name counters...
   local n=$1; shift
   timeout -s KILL 240 rocprofv3 --pmc "$@" -d "$OUT/$n" -o run --output-format csv -- \
-      python3 bench.py --steps 1 --warmup 0 --no-cpu --no-quality "${EXTRA[@]}" > "$OUT/$n.log" 2>&1
+      python3 bench.py --steps 1 --warmup 0 --full --no-cpu --no-quality "${EXTRA[@]}" > "$OUT/$n.log" 2>&1
 }
 run sq1 SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_SCA
 run sq2 SQ_INSTS_VALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INST_CYCLES_VMEM_RD SQ_LEVEL_WAVES SQ_WAVES GRBM_GUI_ACTIVE
