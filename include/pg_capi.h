@@ -358,6 +358,11 @@ pg_status pg_reset_film(void *ctx);
  * (0, 0, -1).  Cleared by pg_reset_film.  Either pointer may be NULL. */
 pg_status pg_read_aovs(void *ctx, float *albedo, float *normal);
 pg_status pg_get_stats(void *ctx, pg_stats *stats);
+/* Path integrator: segments (counted in pg_stats.segments, not in escaped) whose hit was culled by the
+ * closest-hit kernels since create: the ray's next vertex had already lost its Russian roulette, or was past the
+ * depth limit, when the ray was written, and it hit no emitter, so that vertex was never shaded.  0 with
+ * PG_NO_PATH_CULL=1 in the environment.  A read-only entry point: pg_stats keeps its ABI 12 layout. */
+pg_status pg_get_culled(void *ctx, uint64_t *count);
 /* Number of pixels owned by this rank (tile shard). */
 pg_status pg_local_pixel_count(void *ctx, uint64_t *count);
 

@@ -29,11 +29,11 @@ namespace {
 constexpr uint32_t kStackDepth = 48;  // must match STACK_DEPTH in pg_kernels.hip
 constexpr uint32_t kMaxBounces = 1100;     // > gpu_depth_cap default (1024) + 2
 // per-bounce device counters (words): [0, 64) shard counts of the live queue entering the bounce,
-// [64, 128) shadow-queue shard counts, [128, 512) shard counts of the PG_NUM_CLASSES material-class
-// queues followed by the escaped-path counts
+// [64, 128) shadow-queue shard counts, [128, 640) shard counts of the PG_NUM_CLASSES material-class
+// queues followed by the escaped-ray and the culled-hit counts (PG_CLASS_ROWS rows)
 constexpr uint32_t kBounceWords = 640;
 constexpr uint32_t kShadowCounts = PG_QSHARDS, kClassCounts = 2 * PG_QSHARDS;
-static_assert(kClassCounts + (PG_NUM_CLASSES + 1) * PG_QSHARDS <= kBounceWords, "counter layout");
+static_assert(kClassCounts + PG_CLASS_ROWS * PG_QSHARDS <= kBounceWords, "counter layout");
 constexpr uint32_t kCounterWords = kBounceWords * (kMaxBounces + 1);
 // the device's bounce cap (GParams::depth_cap): max_depth + 1 or gpu_depth_cap.  The surface path keeps
 // one counter block per bounce, so its cap is at most kMaxBounces - 2 (pg_create rejects a larger
@@ -249,6 +249,7 @@ struct Ctx {
     ncclComm_t comm = nullptr;
     // stats
     pg_stats stats{};
+    uint64_t culled = 0;  // segments whose hit the tracer culled (pg_get_culled); counted in stats.segments
 };
 
 thread_local std::string g_tls_err;
@@ -898,10 +899,12 @@ pg_status pg_upload_scene(void *ctx, const pg_scene_desc *d) {
     for (uint32_t k = 0; k < nt; ++k) {
         uint32_t t = bvh.order[k];
         packShade(&shade[4 * PG_TRI_SHADE_STRIDE * (size_t)k], d->positions, d->normals, d->indices, t, triBits[t], t);
-        tclass[k] = (uint8_t)materialClass(d->materials[triBits[t] & 0xFFFFu].type);
+        // bit 7: an emitter's triangle, the one hit a doomed ray is kept for (pg_layout.h PF_DOOMED)
+        tclass[k] = (uint8_t)(materialClass(d->materials[triBits[t] & 0xFFFFu].type) |
+                              ((triBits[t] >> 16) != 0 ? PG_TCLASS_EMITTER : 0u));
         // volumetric wavefront: surfaces whose interaction skips the shadow walk through media (delta
         // BSDFs) or ends the path at once (emitters: black in the scenes here) -- VolDev::tcheap
-        tcheap[k] = tclass[k] == PG_CLASS_DELTA || (triBits[t] >> 16) != 0;
+        tcheap[k] = (tclass[k] & PG_TCLASS_MASK) == PG_CLASS_DELTA || (triBits[t] >> 16) != 0;
     }
     // per BVH-order triangle: the shape's medium transition, (interior + 1) | (exterior + 1) << 16
     std::vector<uint32_t> tmed(nt, 0);
@@ -1781,6 +1784,9 @@ static pg_status renderPass(Ctx *c, uint32_t spp, uint32_t sample_offset, int32_
     // are what a render runs; with kernel_timing they are timed as launched (pg_stats rays_ms /
     // shade_ms), so a one-lane calibration context measures the shipped kernels
     const bool fuseRays = !std::getenv("PG_NO_RAYS_FUSION");
+    // PF_DOOMED (pg_layout.h): roulette and depth exits decided one bounce early, doomed non-emitter hits culled
+    // by the tracer; PG_NO_PATH_CULL=1 runs every vertex through the shader as before (same results)
+    g.path_cull = std::getenv("PG_NO_PATH_CULL") ? 0 : 1;
     const bool bands = cameraBands() > 0;
     const bool fuseShade = !c->has_env && !std::getenv("PG_NO_SHADE_FUSION");
     // chunks: whole sample layers over the local pixels when they fit, else pixel ranges
@@ -1798,7 +1804,7 @@ static pg_status renderPass(Ctx *c, uint32_t spp, uint32_t sample_offset, int32_
         return Queue{items, counts, pg_queue_stride(l.P)};
     };
     auto classQueues = [&](const Lane &l, uint32_t *cb, Queue *cls) {
-        for (int k = 0; k <= PG_NUM_CLASSES; ++k)
+        for (int k = 0; k < PG_CLASS_ROWS; ++k)
             cls[k] = lqueue(l, k < PG_NUM_CLASSES ? l.class_q.as<uint32_t>() + (size_t)k * PG_QSHARDS * pg_queue_stride(l.P)
                                                  : nullptr,
                             cb + kClassCounts + k * PG_QSHARDS);
@@ -1807,7 +1813,7 @@ static pg_status renderPass(Ctx *c, uint32_t spp, uint32_t sample_offset, int32_
     // shq: the previous bounce's shadow queue, traced in the same launch (k_rays)
     auto launchTrace = [&](Lane &l, const Queue *shq) -> pg_status {
         uint32_t *cb = l.counters.as<uint32_t>() + (size_t)kBounceWords * l.b;
-        Queue cls[PG_NUM_CLASSES + 1];
+        Queue cls[PG_CLASS_ROWS];
         classQueues(l, cb, cls);
         EventPair et{};
         if (evt) et = nextEvents(&l, shq ? KT_RAYS : KT_TRACE);
@@ -1818,7 +1824,7 @@ static pg_status renderPass(Ctx *c, uint32_t spp, uint32_t sample_offset, int32_
         else pg_launch_trace(l.stream, g, sc, pathView(&l), tq, l.bound, cls, l.b == 0);
         if (evt) HIPC(c, hipEventRecord(et.b, l.stream));
         HIPC(c, hipMemcpyAsync(l.h_counts + (size_t)kBounceWords * l.b + kClassCounts, cb + kClassCounts,
-                               (PG_NUM_CLASSES + 1) * PG_QSHARDS * 4, hipMemcpyDeviceToHost, l.stream));
+                               PG_CLASS_ROWS * PG_QSHARDS * 4, hipMemcpyDeviceToHost, l.stream));
         HIPC(c, hipEventRecord(l.ready, l.stream));
         return PG_OK;
     };
@@ -1832,10 +1838,11 @@ static pg_status renderPass(Ctx *c, uint32_t spp, uint32_t sample_offset, int32_
         c->stats.segments += l.h_tail[0];  // the chunk's tail (k_tail)
         c->stats.escaped += l.h_tail[1];
         c->stats.shadow_rays += l.h_tail[2];
+        c->culled += l.h_tail[3];
         if (std::getenv("PG_DEBUG_COUNTS")) {
             for (uint32_t k = 0; k < l.stats_bounces && k < l.used_prev.size(); ++k) {
                 uint64_t t = 0;
-                for (int w = 0; w < (PG_NUM_CLASSES + 1) * PG_QSHARDS; ++w)
+                for (int w = 0; w < PG_CLASS_ROWS * PG_QSHARDS; ++w)
                     t += l.h_stats[(size_t)kBounceWords * k + kClassCounts + w];
                 if (t != l.used_prev[k])
                     std::fprintf(stderr, "PG_DEBUG_COUNTS: chunk bounce %u: host read %llu segments, device %llu\n", k,
@@ -1884,7 +1891,7 @@ static pg_status renderPass(Ctx *c, uint32_t spp, uint32_t sample_offset, int32_
         l.chunk = nextChunk++;
         HIPC(c, hipStreamWaitEvent(l.stream, c->pass_start, 0));
         HIPC(c, hipMemsetAsync(l.counters.p, 0, (size_t)kBounceWords * (maxBounces + 1) * 4, l.stream));
-        HIPC(c, hipMemsetAsync(l.tail_stats.p, 0, 24, l.stream));
+        HIPC(c, hipMemsetAsync(l.tail_stats.p, 0, 32, l.stream));
         pg_launch_camera(l.stream, g, pathView(&l), c->d_band_pixels.as<uint32_t>(), l.pb, l.np, l.nl,
                          sample_offset + l.layer0, lqueue(l, l.q0.as<uint32_t>(), l.counters.as<uint32_t>()), bands);
         return launchTrace(l, nullptr);
@@ -1895,7 +1902,7 @@ static pg_status renderPass(Ctx *c, uint32_t spp, uint32_t sample_offset, int32_
         if ((st = collectStats(l))) return st;
         const PathDev pv = pathView(&l);
         HIPC(c, hipMemcpyAsync(l.h_stats, l.counters.p, (size_t)kBounceWords * l.b * 4, hipMemcpyDeviceToHost, l.stream));
-        HIPC(c, hipMemcpyAsync(l.h_tail, l.tail_stats.p, 24, hipMemcpyDeviceToHost, l.stream));
+        HIPC(c, hipMemcpyAsync(l.h_tail, l.tail_stats.p, 32, hipMemcpyDeviceToHost, l.stream));
         HIPC(c, hipStreamWaitEvent(l.stream, c->film_order, 0));
         pg_launch_film(l.stream, g, sc, pv, c->d_band_pixels.as<uint32_t>(), l.pb, l.np, l.nl, c->film.as<float4>(),
                        c->film_sq.as<float4>(), c->aov_albedo.as<float4>(), c->aov_normal.as<float4>());
@@ -1933,13 +1940,13 @@ static pg_status renderPass(Ctx *c, uint32_t spp, uint32_t sample_offset, int32_
         const uint32_t *hc = l.h_counts + (size_t)kBounceWords * l.b + kClassCounts;
         uint32_t clsMax[PG_NUM_CLASSES], shardLive[PG_QSHARDS] = {};
         uint64_t nlive = 0;
-        for (int k = 0; k <= PG_NUM_CLASSES; ++k) {
+        for (int k = 0; k < PG_CLASS_ROWS; ++k) {
             uint32_t m = 0;
             for (int sh = 0; sh < PG_QSHARDS; ++sh) {
                 const uint32_t v = hc[k * PG_QSHARDS + sh];
                 c->stats.segments += v;
-                if (k == PG_NUM_CLASSES) {
-                    c->stats.escaped += v;
+                if (k >= PG_NUM_CLASSES) {  // counted only: neither shaded nor alive
+                    (k == PG_CLASS_ESCAPED ? c->stats.escaped : c->culled) += v;
                     continue;
                 }
                 m = std::max(m, v);
@@ -1950,7 +1957,7 @@ static pg_status renderPass(Ctx *c, uint32_t spp, uint32_t sample_offset, int32_
         }
         {
             uint64_t t = 0;
-            for (int w = 0; w < (PG_NUM_CLASSES + 1) * PG_QSHARDS; ++w) t += hc[w];
+            for (int w = 0; w < PG_CLASS_ROWS * PG_QSHARDS; ++w) t += hc[w];
             l.used_cur.push_back(t);
         }
         ++l.b;
@@ -1979,7 +1986,7 @@ static pg_status renderPass(Ctx *c, uint32_t spp, uint32_t sample_offset, int32_
             }
             return PG_OK;
         }
-        Queue cls[PG_NUM_CLASSES + 1];
+        Queue cls[PG_CLASS_ROWS];
         classQueues(l, cb, cls);
         const PathDev pv = pathView(&l);
         Queue next = lqueue(l, (l.b & 1) ? l.q1.as<uint32_t>() : l.q0.as<uint32_t>(), cb + kBounceWords);
@@ -2466,6 +2473,13 @@ pg_status pg_get_stats(void *ctx, pg_stats *st) {
     Ctx *c = (Ctx *)ctx;
     if (!c || !st) return fail(c, PG_ERR_INVALID, "pg_get_stats: null argument");
     *st = c->stats;
+    return PG_OK;
+}
+
+pg_status pg_get_culled(void *ctx, uint64_t *count) {
+    Ctx *c = (Ctx *)ctx;
+    if (!c || !count) return fail(c, PG_ERR_INVALID, "pg_get_culled: null argument");
+    *count = c->culled;
     return PG_OK;
 }
 

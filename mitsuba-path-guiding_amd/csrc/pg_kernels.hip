@@ -129,15 +129,30 @@ __device__ __forceinline__ float4 envHitRadiance(float4 L, float4 hv) {
 }
 
 
+// PF_DOOMED on the ray (pg_layout.h): shadeOne stores a doomed extension ray's tmin negated
+__device__ __forceinline__ bool rayDoomed(float4 o) { return (__float_as_uint(o.w) >> 31) != 0; }
+// class-queue row of a traced ray: the hit triangle's material class, PG_CLASS_ESCAPED for a miss, or
+// PG_CLASS_CULLED for a doomed ray that hit a non-emitter -- its vertex would do nothing, so the path ends
+// here and its hit record becomes a miss without environment radiance (k_film / k_commit add exact zeros)
+__device__ __forceinline__ int hitClass(const SceneDev &sc, bool h, uint32_t tri, bool doomed, float4 &hr) {
+    if (!h) return PG_CLASS_ESCAPED;
+    const uint32_t tc = sc.tclass[tri];
+    if (doomed && !(tc & PG_TCLASS_EMITTER)) {
+        hr = make_float4(0.0f, __uint_as_float(0xFFFFFFFFu), 0.0f, 0.0f);
+        return PG_CLASS_CULLED;
+    }
+    return (int)(tc & PG_TCLASS_MASK);
+}
+
 // closest hit for every queued path: hit[slot] = (t, BVH-order triangle | ~0, u, v).
 // Grid-stride over the queue shard blockIdx % PG_QSHARDS.  (A persistent variant with dynamic
 // ray fetch into finished lanes measured slower once traversal was made while-while.)
 struct ClassQueues {
-    Queue q[PG_NUM_CLASSES + 1];
+    Queue q[PG_CLASS_ROWS];
 };
 
 // wave-aggregated append of `slot` to class queue `cls` (< 0: none), shard s: one atomic per class
-// present in the wave; class PG_NUM_CLASSES (escaped paths) is counted only
+// present in the wave; the rows from PG_NUM_CLASSES on (escaped rays, culled hits) are counted only
 __device__ __forceinline__ void classAppend(int cls, uint32_t slot, const ClassQueues &cqs, uint32_t s) {
     const int lane = threadIdx.x & 63;
     unsigned long long pending = __ballot(cls >= 0);
@@ -182,23 +197,29 @@ __device__ __forceinline__ void traceRows(const GParams &g, const SceneDev &sc, 
         if (i < n) {
             slot = items[i];
             float4 o = ldS(&p.ray_o[slot]), d = ldS(&p.ray_d[slot]);
+            // the doomed bit rides through the walk in the slot's top bit (slots are < 2^31): no register of its own
+            // under k_rays' 64-VGPR cap
+            slot |= rayDoomed(o) ? 0x80000000u : 0u;
+            const float tmin = fabsf(o.w);
             float tmax = d.w;
             uint32_t tri = 0xFFFFFFFFu;
             float u = 0, v = 0;
             bool h;
             if constexpr (WIDE)
-                h = traverseWide<false>(sc.wnodes, sc.wtris, xyz(o), xyz(d), o.w, tmax, tri, u, v,
+                h = traverseWide<false>(sc.wnodes, sc.wtris, xyz(o), xyz(d), tmin, tmax, tri, u, v,
                                         WStack{stk.lds, stk.ovf, stk.ostride});
             else
-                h = traverse<false, LTOP>(sc.nodes, sc.tris, xyz(o), xyz(d), o.w, tmax, tri, u, v, stk, top, ntop);
+                h = traverse<false, LTOP>(sc.nodes, sc.tris, xyz(o), xyz(d), tmin, tmax, tri, u, v, stk, top, ntop);
+            const bool doomed = (slot >> 31) != 0;
+            slot &= 0x7FFFFFFFu;
             float4 hr = make_float4(h ? tmax : 0.0f, __uint_as_float(h ? tri : 0xFFFFFFFFu), u, v);
             if (first) first[slot] = hr;
             if (ENV && !h) {
                 const f3 e = envEscapeRadiance(g, sc, p, slot, xyz(d));
                 hr = make_float4(e.x, hr.y, e.y, e.z);
             }
+            cls = hitClass(sc, h, tri, doomed, hr);
             stS(&p.hit[slot], hr);
-            cls = h ? (int)sc.tclass[tri] : PG_NUM_CLASSES;
         }
         classAppend(cls, slot, cqs, s);
     }
@@ -235,7 +256,7 @@ __device__ __forceinline__ void traceRowsPersist(const GParams &g, const SceneDe
     uint32_t cur = min(n, wv * per);
     const uint32_t end = min(n, cur + per);
     const int lane = threadIdx.x & 63;
-    bool active = false;
+    bool active = false, doomed = false;
     uint32_t slot = 0;
     Walk4 w;
     for (;;) {
@@ -246,7 +267,8 @@ __device__ __forceinline__ void traceRowsPersist(const GParams &g, const SceneDe
             if (!active && cur + rank < end) {
                 slot = items[cur + rank];
                 const float4 o = ldS(&p.ray_o[slot]), d = ldS(&p.ray_d[slot]);
-                walk4Start(w, xyz(o), xyz(d), o.w, d.w);
+                doomed = rayDoomed(o);
+                walk4Start(w, xyz(o), xyz(d), fabsf(o.w), d.w);
                 active = true;
             }
             cur += min(idle, end - cur);
@@ -263,8 +285,8 @@ __device__ __forceinline__ void traceRowsPersist(const GParams &g, const SceneDe
                 const f3 e = envEscapeRadiance(g, sc, p, slot, w.d);
                 hr = make_float4(e.x, hr.y, e.y, e.z);
             }
+            cls = hitClass(sc, h, w.hitTri, doomed, hr);
             stS(&p.hit[slot], hr);
-            cls = h ? (int)sc.tclass[w.hitTri] : PG_NUM_CLASSES;
             active = false;
         }
         classAppend(cls, slot, cqs, s);
@@ -281,7 +303,7 @@ __device__ __forceinline__ void traceRowsPersist(const GParams &g, const SceneDe
 constexpr uint32_t kPairRing = PG_QSTACK_DEPTH - LDS_STACK;
 template <bool ENV>
 __device__ __forceinline__ void finishWalk(const GParams &g, const SceneDev &sc, const PathDev &p, const Walk4 &w,
-                                           uint32_t slot, float4 *first, int &cls) {
+                                           uint32_t slot, bool doomed, float4 *first, int &cls) {
     const bool h = w.hitTri != 0xFFFFFFFFu;
     float4 hr = make_float4(h ? w.tmax : 0.0f, __uint_as_float(h ? w.hitTri : 0xFFFFFFFFu), w.hu, w.hv);
     if (first) first[slot] = hr;
@@ -289,8 +311,8 @@ __device__ __forceinline__ void finishWalk(const GParams &g, const SceneDev &sc,
         const f3 e = envEscapeRadiance(g, sc, p, slot, w.d);
         hr = make_float4(e.x, hr.y, e.y, e.z);
     }
+    cls = hitClass(sc, h, w.hitTri, doomed, hr);
     stS(&p.hit[slot], hr);
-    cls = h ? (int)sc.tclass[w.hitTri] : PG_NUM_CLASSES;
 }
 template <bool ENV>
 __device__ __forceinline__ void traceRowsPair(const GParams &g, const SceneDev &sc, const PathDev &p, const Queue &q,
@@ -302,23 +324,26 @@ __device__ __forceinline__ void traceRowsPair(const GParams &g, const SceneDev &
     for (uint32_t base = (bid / PG_QSHARDS) * 2 * TRACE_BLOCK; base < n; base += nblk / PG_QSHARDS * 2 * TRACE_BLOCK) {
         const uint32_t ia = base + threadIdx.x, ib = ia + TRACE_BLOCK;
         uint32_t slotA = 0, slotB = 0;
+        bool doomedA = false, doomedB = false;
         Walk4 a, b;
         walk4Idle(a);
         walk4Idle(b);
         if (ia < n) {
             slotA = items[ia];
             const float4 o = ldS(&p.ray_o[slotA]), d = ldS(&p.ray_d[slotA]);
-            walk4Start(a, xyz(o), xyz(d), o.w, d.w);
+            doomedA = rayDoomed(o);
+            walk4Start(a, xyz(o), xyz(d), fabsf(o.w), d.w);
         }
         if (ib < n) {
             slotB = items[ib];
             const float4 o = ldS(&p.ray_o[slotB]), d = ldS(&p.ray_d[slotB]);
-            walk4Start(b, xyz(o), xyz(d), o.w, d.w);
+            doomedB = rayDoomed(o);
+            walk4Start(b, xyz(o), xyz(d), fabsf(o.w), d.w);
         }
         walk4Pair(a, b, sc.nodes, sc.tris, sa, sb);
         int ca = -1, cb = -1;
-        if (ia < n) finishWalk<ENV>(g, sc, p, a, slotA, first, ca);
-        if (ib < n) finishWalk<ENV>(g, sc, p, b, slotB, first, cb);
+        if (ia < n) finishWalk<ENV>(g, sc, p, a, slotA, doomedA, first, ca);
+        if (ib < n) finishWalk<ENV>(g, sc, p, b, slotB, doomedB, first, cb);
         classAppend(ca, slotA, cqs, s);
         classAppend(cb, slotB, cqs, s);
     }
@@ -509,6 +534,8 @@ __device__ __forceinline__ void shadeOne(const GParams &g, const SceneDev &sc, c
                                          uint32_t &rkey) {
     bool dirtyL = false;
     f3 L = mk1(0.f);
+    // the watch build logs every vertex with its own roulette draw, as the oracle does
+    const bool cull = !PG_WATCH && g.path_cull;
 #if PG_WATCH
     float wr[PG_WATCH_F];
     for (int i = 0; i < PG_WATCH_F; ++i) wr[i] = -1.0f;
@@ -575,19 +602,27 @@ __device__ __forceinline__ void shadeOne(const GParams &g, const SceneDev &sc, c
                 L = L + T * Le * w;
                 dirtyL = true;
             }
+            // PF_DOOMED (pg_layout.h): the previous vertex's shader made this vertex's exits for it, and the
+            // tracer kept the path only because it hit an emitter
+            if (flags & PF_DOOMED) break;
             if (depth - 1 >= (uint32_t)g.rr_depth) {
                 float q = fminf(maxc(T) * eta * eta, 0.95f);
                 WSET(26, q);
                 WSET3(18, L);
                 WSET3(5, T);
                 WSET(27, 0);
-                if (rng1(key, sample, dimOf(depth - 1, SLOT_RR)) >= q) break;
+                // with the cull on, a vertex that got here has already survived this draw
+                if (!cull && rng1(key, sample, dimOf(depth - 1, SLOT_RR)) >= q) break;
                 WSET(27, 1);
                 T = T / q;
             }
         }
         WSET3(5, T);
         if (depth > g.depth_cap) break;
+        // the next vertex's roulette draw (PF_DOOMED), made where this vertex's own used to be: here Philox costs
+        // the registers it always did (k_shade_all spills 4 VGPRs); next to the extension-ray stores it spilled 49
+        float rrNext = 0.0f;
+        if (cull && depth >= (uint32_t)g.rr_depth) rrNext = rng1(key, sample, dimOf(depth, SLOT_RR));
 #if PG_MAT_UNIFORM
         // one uniform (scalar-cache) load per distinct material of the wave instead of eight 16-B gathers per lane
         GMat M;
@@ -746,11 +781,21 @@ __device__ __forceinline__ void shadeOne(const GParams &g, const SceneDev &sc, c
                     nv++;
                 }
                 float tmin = kEpsilon * fmaxf(fmaxf(fmaxf(fabsf(h.p.x), fabsf(h.p.y)), fabsf(h.p.z)), kEpsilon);
-                stS(&p.ray_o[slot], f4(h.p, tmin));
+                const float etaN = eta * bs.eta;
+                // the next vertex's exits, decided here (PF_DOOMED): its depth tests, and its roulette draw against
+                // the throughput and eta it will load from thr[slot]
+                bool doomed = false;
+                if (cull) {
+                    const uint32_t D = depth + 1;
+                    doomed = D > g.depth_cap || (g.max_depth > 0 && (int)D >= g.max_depth) ||
+                             (D - 1 >= (uint32_t)g.rr_depth && rrNext >= fminf(maxc(Tn) * etaN * etaN, 0.95f));
+                }
+                stS(&p.ray_o[slot], f4(h.p, doomed ? -tmin : tmin));
                 stS(&p.ray_d[slot], f4(wo, __int_as_float(0x7f800000)));
-                stS(&p.thr[slot], f4(Tn, eta * bs.eta));
+                stS(&p.thr[slot], f4(Tn, etaN));
                 stS(&p.prev[slot], f4(refN, woPdf));
-                flags = (flags & ~(PF_EMITTED_QUERY | PF_PREV_DELTA)) | ((bs.type & EDelta) ? PF_PREV_DELTA : 0u);
+                flags = (flags & ~(PF_EMITTED_QUERY | PF_PREV_DELTA)) | ((bs.type & EDelta) ? PF_PREV_DELTA : 0u) |
+                        (doomed ? PF_DOOMED : 0u);
                 stPinfoZW(&p.pinfo[slot], (depth + 1) | (flags << 16), nv);
                 alive = true;
                 if (wantKey) rkey = rayOrderKey(sd, h.p, wo);
@@ -921,12 +966,12 @@ __global__ __launch_bounds__(256) void k_rsort_scatter(Queue q, uint32_t *hist, 
 // wavefront's own code on the path's own state and random numbers, in the same order (a path's NEE
 // is added before its next vertex is shaded), so films, records and trees are bit-identical with
 // the bounce-by-bounce loop.  Input: the queue of the bounce just traced (hits already in p.hit).
-// stats: [0] traced segments, [1] escaped segments, [2] shadow rays (u64, device atomics).
+// stats: [0] traced segments, [1] escaped segments, [2] shadow rays, [3] culled hits (u64, device atomics).
 template <bool ENV>
 __device__ __forceinline__ void tailShade(const GParams &g, const SceneDev &sc, const SDDev &sd, const PathDev &p,
                                           uint32_t slot, uint32_t tri, bool &alive, bool &shadow) {
     uint32_t rk = 0;
-    switch (sc.tclass[tri]) {
+    switch (sc.tclass[tri] & PG_TCLASS_MASK) {
         case PG_CLASS_DIFFUSE: shadeOne<PG_BSDF_DIFFUSE, true, ENV>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, rk); break;
         case PG_CLASS_ROUGHCONDUCTOR:
             shadeOne<PG_BSDF_ROUGHCONDUCTOR, true, ENV>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, rk);
@@ -953,7 +998,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PG_
     const uint32_t s = blockIdx.x & (PG_QSHARDS - 1);
     const uint32_t rows = gridDim.x / PG_QSHARDS;  // grid capped at TRACE_MAX_BLOCKS: the overflow ring's size
     const uint32_t n = q.counts[s];
-    uint32_t segs = 0, esc = 0, shadows = 0;
+    uint32_t segs = 0, esc = 0, shadows = 0, culled = 0;
     for (uint32_t i = (blockIdx.x / PG_QSHARDS) * TRACE_BLOCK + threadIdx.x; i < n; i += rows * TRACE_BLOCK) {
         const uint32_t slot = q.items[(size_t)s * q.stride + i];
         uint32_t tri = __float_as_uint(ldS(&p.hit[slot]).y);
@@ -980,31 +1025,33 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PG_
             const float4 o = ldS(&p.ray_o[slot]), d = ldS(&p.ray_d[slot]);
             float tmax = d.w, u = 0, v = 0;
             tri = 0xFFFFFFFFu;
-            const bool h = traverse<false>(sc.nodes, sc.tris, xyz(o), xyz(d), o.w, tmax, tri, u, v, stk);
+            const bool h = traverse<false>(sc.nodes, sc.tris, xyz(o), xyz(d), fabsf(o.w), tmax, tri, u, v, stk);
             float4 hr = make_float4(h ? tmax : 0.0f, __uint_as_float(h ? tri : 0xFFFFFFFFu), u, v);
             if (ENV && !h) {
                 const f3 e = envEscapeRadiance(g, sc, p, slot, xyz(d));
                 hr = make_float4(e.x, hr.y, e.y, e.z);
             }
+            const int cls = hitClass(sc, h, tri, rayDoomed(o), hr);
             stS(&p.hit[slot], hr);
             ++segs;
-            if (!h) {
-                ++esc;
-                tri = 0xFFFFFFFFu;
-            }
+            if (cls == PG_CLASS_ESCAPED) ++esc;
+            if (cls == PG_CLASS_CULLED) ++culled;
+            if (cls >= PG_NUM_CLASSES) tri = 0xFFFFFFFFu;  // the path ended with this segment
         }
     }
     // wave-summed counters
-    unsigned long long a = segs, b = esc, c = shadows;
+    unsigned long long a = segs, b = esc, c = shadows, e = culled;
     for (int off = 32; off > 0; off >>= 1) {
         a += __shfl_xor(a, off);
         b += __shfl_xor(b, off);
         c += __shfl_xor(c, off);
+        e += __shfl_xor(e, off);
     }
     if ((threadIdx.x & 63) == 0 && (a | b | c)) {
         atomicAdd(stats + 0, a);
         atomicAdd(stats + 1, b);
         atomicAdd(stats + 2, c);
+        if (e) atomicAdd(stats + 3, e);
     }
 }
 
@@ -1451,7 +1498,7 @@ void pg_launch_trace(hipStream_t s, const GParams &g, const SceneDev &sc, const 
                      const Queue *class_queues, bool first_bounce) {
     if (!max_shard) return;
     ClassQueues cq;
-    for (int c = 0; c <= PG_NUM_CLASSES; ++c) cq.q[c] = class_queues[c];
+    for (int c = 0; c < PG_CLASS_ROWS; ++c) cq.q[c] = class_queues[c];
     const dim3 grid = shardGrid(max_shard, TRACE_BLOCK, TRACE_MAX_BLOCKS / PG_QSHARDS);
     float4 *first = first_bounce ? p.aov : nullptr;
     if (sc.env) hipLaunchKernelGGL(k_trace<true>, grid, dim3(TRACE_BLOCK), 0, s, g, sc, p, q, cq, first);
@@ -1498,14 +1545,14 @@ void pg_launch_shade_all(hipStream_t s, const GParams &g, const SceneDev &sc, co
         total += max_shard[c] ? shardGrid(max_shard[c], SHADE_BLOCK, 0xFFFFFFFFu).x : 0;
         r.end[c] = total;
     }
-    cq.q[PG_NUM_CLASSES] = class_queues[PG_NUM_CLASSES];
+    for (int c = PG_NUM_CLASSES; c < PG_CLASS_ROWS; ++c) cq.q[c] = class_queues[c];
     if (!total) return;
     hipLaunchKernelGGL(k_shade_all, dim3(total), dim3(SHADE_BLOCK), 0, s, g, sc, sd, p, cq, out, shq, r);
 }
 void pg_launch_rays(hipStream_t s, const GParams &g, const SceneDev &sc, const PathDev &p, Queue q, uint32_t max_shard,
                     const Queue *class_queues, Queue shq, uint32_t max_shadow_shard) {
     ClassQueues cq;
-    for (int c = 0; c <= PG_NUM_CLASSES; ++c) cq.q[c] = class_queues[c];
+    for (int c = 0; c < PG_CLASS_ROWS; ++c) cq.q[c] = class_queues[c];
     const uint32_t sb = max_shadow_shard ? shardGrid(max_shadow_shard, TRACE_BLOCK, TRACE_MAX_BLOCKS / PG_QSHARDS).x : 0;
     const uint32_t tb =
         max_shard ? shardGrid(max_shard, (PG_TRACE_PAIR ? 2 : 1) * TRACE_BLOCK, TRACE_MAX_BLOCKS / PG_QSHARDS).x : 0;

@@ -244,11 +244,28 @@ inline void pg_qnode_box(const float *node, int s, float lo[3], float hi[3]) {
 #define PG_CLASS_ROUGHPLASTIC 4
 #define PG_CLASS_DELTA 5
 #define PG_NUM_CLASSES 6
+// counted-only rows after the class queues' shard counts: escaped rays, then culled hits (PF_DOOMED below)
+#define PG_CLASS_ESCAPED PG_NUM_CLASSES
+#define PG_CLASS_CULLED (PG_NUM_CLASSES + 1)
+#define PG_CLASS_ROWS (PG_NUM_CLASSES + 2)
+// SceneDev::tclass[tri]: the class in the low bits, bit 7 set on an emitter's triangles
+#define PG_TCLASS_EMITTER 0x80u
+#define PG_TCLASS_MASK 0x7Fu
 
-// Path-state flags (pinfo.z high bits)
+// Path-state flags (pinfo.z high bits; stPinfoZW writes depth | flags << 16 with the vertex count)
 #define PF_SCATTERED 0x1u
 #define PF_EMITTED_QUERY 0x2u
 #define PF_PREV_DELTA 0x4u
+// The vertex this ray leads to ends before it samples anything: the shader that wrote the ray already made its
+// Russian-roulette draw (same key, sample, dimension, throughput and eta the vertex would use) and lost, or the
+// vertex is past depth_cap / at max_depth.  Such a vertex can only add the emission of an emitter it hits, so
+//   - the ray carries the bit in the sign of ray_o.w (tmin > 0; the closest-hit walks take |w|), and a doomed ray
+//     that hits a non-emitter is culled by the tracer: its hit record is stored as a miss (0, ~0, 0, 0), it joins
+//     no class queue and is counted in the PG_CLASS_CULLED row;
+//   - a doomed ray that hits an emitter is shaded: shadeOne adds the MIS-weighted emission, sees PF_DOOMED and
+//     stops where the roulette draw used to be.
+// Set only while GParams::path_cull is on; then a vertex without the flag has survived its roulette.
+#define PF_DOOMED 0x8u
 
 // Kernel-side constants of one render context.
 struct GParams {
@@ -263,4 +280,5 @@ struct GParams {
     int32_t fraction_bound;  // pg_config.bsdf_fraction_bound (PG_FRACTION_*)
     int32_t exact_mis;       // pg_config.volpath_exact_mis
     int32_t glossy_prior;    // pg_config.glossy_prior
+    int32_t path_cull;       // 1: shadeOne decides PF_DOOMED one bounce early and the tracer culls (PG_NO_PATH_CULL: 0)
 };

@@ -1169,7 +1169,7 @@ __device__ __forceinline__ uint16_t flightKey(const VolDev &v, int m, f3 o, f3 d
 #endif
 __device__ __forceinline__ bool cheapSurface(const SceneDev &sc, const VolDev &v, bool valid, uint32_t tri) {
     return PG_VOL_SPLIT_SURF &&
-           (!valid || (PG_VOL_SPLIT_EMIT ? v.tcheap[tri] != 0 : sc.tclass[tri] == PG_CLASS_DELTA));
+           (!valid || (PG_VOL_SPLIT_EMIT ? v.tcheap[tri] != 0 : (sc.tclass[tri] & PG_TCLASS_MASK) == PG_CLASS_DELTA));
 }
 __device__ __forceinline__ void surfAppend(bool pred, bool cheap, uint32_t slot, const Queue &qs, const Queue &qd,
                                            uint32_t sh) {

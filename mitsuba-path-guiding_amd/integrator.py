@@ -239,7 +239,11 @@ class Device:
     def stats(self):
         s = capi.pg_stats()
         self._chk(self.lib.pg_get_stats(self.h, C.byref(s)))
-        return {k: getattr(s, k) for k, _ in capi.pg_stats._fields_}
+        out = {k: getattr(s, k) for k, _ in capi.pg_stats._fields_}
+        n = C.c_uint64()
+        self._chk(self.lib.pg_get_culled(self.h, C.byref(n)))
+        out["culled"] = n.value  # segments whose doomed vertex the tracer culled (pg_capi.h pg_get_culled)
+        return out
 
     def local_pixel_count(self):
         n = C.c_uint64()
