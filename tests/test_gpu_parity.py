@@ -386,14 +386,36 @@ def test_sdtree_deep_lookup_matches_oracle(pg, O, scenes):
 
 
 def test_guided_training_parity(pg, O, scenes):
-    """Guided training on GPU vs oracle: same number of records per iteration (within MC noise),
-    and the guided image agrees with the unguided oracle image (guiding is unbiased)."""
+    """Guided training on GPU vs oracle: every iteration writes as many records as an oracle pass with the same
+    tree and streams (within 0.1 %, measured 12863 / 12863, 13311 / 13311, 43008 / 43005, 84920 / 84920; what
+    is in the records: tests/test_gpu_records.py), and the guided image agrees with the unguided oracle image
+    (guiding is unbiased)."""
     sc = scenes["cornell"]
     from mitsuba_path_guiding_amd.integrator import GuidedPathTracer
     integ = GuidedPathTracer({"trainingIterations": 4, "sTreeThreshold": 400.0})
     integ.preprocess(sc)
+    osc = O.OracleScene(pg.capi, sc)
+    otree = O.OracleSDTree(osc)
+    counts = []
+    splat_and_refit = integ.postprogression_train
+
+    def count_then_train(it):  # after iteration it's pass, before its records are splatted
+        spp = 2 ** it
+        otree.deserialize(integ.dev.get_sdtree())  # the tree the pass just sampled
+        n_cpu = int(O.render(osc, integ.cfg, spp, sample_offset=integ.sample_offset - spp, record=True, sdtree=otree,
+                             nthreads=16)[2][3])
+        otree.take_records(pg.capi)
+        counts.append((integ.dev.record_count(), n_cpu))
+        splat_and_refit(it)
+
+    integ.postprogression_train = count_then_train
     rgbw, sq = integ.render(128)
     st = integ.postprocess()
+    print("records per training iteration (gpu, oracle):", counts)
+    assert len(counts) == 4
+    for n_gpu, n_cpu in counts:
+        assert n_cpu > 1000 and abs(n_gpu - n_cpu) <= 0.001 * n_cpu, counts
+    assert st["records"] == sum(n for n, _ in counts)
     assert st["records"] > 0 and st["stree_nodes"] > 1
     cfgu = pg.capi.default_config()
     c = O.render(O.OracleScene(pg.capi, sc), cfgu, 512)[:2]
