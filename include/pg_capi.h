@@ -363,6 +363,13 @@ pg_status pg_get_stats(void *ctx, pg_stats *stats);
  * depth limit, when the ray was written, and it hit no emitter, so that vertex was never shaded.  0 with
  * PG_NO_PATH_CULL=1 in the environment.  A read-only entry point: pg_stats keeps its ABI 12 layout. */
 pg_status pg_get_culled(void *ctx, uint64_t *count);
+/* Path integrator: segments since create that an any-hit probe answered instead of the closest-hit walk (the doom
+ * probe): the ray's next vertex was already lost, as for pg_get_culled, and the ray misses every padded box over
+ * the emitter triangles, so only whether it hits anything was still wanted.  Each is counted in pg_stats.segments
+ * and in pg_get_culled (it hit something) or pg_stats.escaped (it did not), as when it was traced.  0 with
+ * PG_NO_DOOM_PROBE=1 or PG_NO_PATH_CULL=1 in the environment, and for scenes with an environment emitter.  A
+ * read-only entry point like pg_get_culled: pg_stats keeps its ABI 12 layout. */
+pg_status pg_get_probes(void *ctx, uint64_t *count);
 /* Number of pixels owned by this rank (tile shard). */
 pg_status pg_local_pixel_count(void *ctx, uint64_t *count);
 

@@ -30,10 +30,12 @@ constexpr uint32_t kStackDepth = 48;  // must match STACK_DEPTH in pg_kernels.hi
 constexpr uint32_t kMaxBounces = 1100;     // > gpu_depth_cap default (1024) + 2
 // per-bounce device counters (words): [0, 64) shard counts of the live queue entering the bounce,
 // [64, 128) shadow-queue shard counts, [128, 640) shard counts of the PG_NUM_CLASSES material-class
-// queues followed by the escaped-ray and the culled-hit counts (PG_CLASS_ROWS rows)
-constexpr uint32_t kBounceWords = 640;
+// queues followed by the escaped-ray and the culled-hit counts (PG_CLASS_ROWS rows), [640, 704) shard counts of the
+// probe queue the bounce's shading fills (pg_layout.h "Doom probe")
+constexpr uint32_t kBounceWords = 704;
 constexpr uint32_t kShadowCounts = PG_QSHARDS, kClassCounts = 2 * PG_QSHARDS;
-static_assert(kClassCounts + PG_CLASS_ROWS * PG_QSHARDS <= kBounceWords, "counter layout");
+constexpr uint32_t kProbeCounts = kClassCounts + PG_CLASS_ROWS * PG_QSHARDS;
+static_assert(kProbeCounts + PG_QSHARDS <= kBounceWords, "counter layout");
 constexpr uint32_t kCounterWords = kBounceWords * (kMaxBounces + 1);
 // the device's bounce cap (GParams::depth_cap): max_depth + 1 or gpu_depth_cap.  The surface path keeps
 // one counter block per bounce, so its cap is at most kMaxBounces - 2 (pg_create rejects a larger
@@ -130,15 +132,16 @@ uint64_t smallPass() {
 #define PG_PIXEL_BLOCK 8  // local pixel order inside a tile: 8x8 blocks (0: row-major)
 #endif
 #define PG_DEFAULT_LANES 3
+constexpr size_t kTailStats = 5;  // k_tail: segments, escaped, shadow rays, culled, probes
 struct Lane {
     hipStream_t stream = nullptr;
     uint32_t P = 0;
     int vtx_slots = 0;
     uint32_t vtxP = 0;  // slot stride of vtx (recording passes only allocate it)
-    DevBuf ray_o, ray_d, hit, thr, rad, prev, pinfo, sh_d, sh_c, vtx, q0, q1, qs, class_q, counters, stack_ovf;
+    DevBuf ray_o, ray_d, hit, thr, rad, prev, pinfo, sh_d, sh_c, vtx, q0, q1, qs, qp, class_q, counters, stack_ovf;
     DevBuf qkey, qsorted, rsort_hist;  // ray-sorted trace queues (PG_RAY_SORT): keys, sorted entries, histograms
     bool sorted = false;               // the queue of the next trace launch is qsorted
-    DevBuf tail_stats;                 // k_tail counters of the running chunk (3 u64), copied to h_tail
+    DevBuf tail_stats;                 // k_tail counters of the running chunk (kTailStats u64), copied to h_tail
     uint64_t *h_tail = nullptr;        // pinned: k_tail counters of the last finished chunk
     DevBuf aov;  // denoiser features per slot (pg_config.aovs), 2 x float4
     uint32_t *h_counts = nullptr;  // pinned: per-bounce class counts of the running chunk
@@ -210,6 +213,10 @@ struct Ctx {
     uint32_t vol_cap = 0;
     uint32_t num_tris = 0, num_mats = 0;
     uint32_t bvh_top_nodes = 0;  // breadth-first top levels of the binary BVH (staged in LDS by k_trace)
+    // padded boxes over the emitter triangles (pg_layout.h "Doom probe"): SceneDev::em_box
+    uint32_t num_em_boxes = 0;
+    float em_absmax = 0.0f;
+    float em_box[PG_EMBOX_MAX][6] = {};
     std::vector<GMat> host_mats;
     float scene_lo[3] = {0, 0, 0}, scene_hi[3] = {0, 0, 0};
     // shard
@@ -250,6 +257,7 @@ struct Ctx {
     // stats
     pg_stats stats{};
     uint64_t culled = 0;  // segments whose hit the tracer culled (pg_get_culled); counted in stats.segments
+    uint64_t probes = 0;  // segments answered by an any-hit probe (pg_get_probes); counted in culled or escaped
 };
 
 thread_local std::string g_tls_err;
@@ -392,11 +400,15 @@ pg_status upload(Ctx *c, DevBuf &b, const std::vector<T> &v) {
 }
 
 SceneDev sceneView(const Ctx *c) {
-    return SceneDev{c->nodes.as<float4>(), c->tris.as<float4>(), c->wnodes.as<float4>(), c->tris.as<float4>(),
-                    c->tshade.as<float4>(), c->tclass.as<uint8_t>(),
-                    c->mats.as<GMat>(),
-                    c->ems.as<GEmitter>(), c->emtri.as<float4>(), c->emcdf.as<float>(),
-                    c->has_env ? c->env.as<GEnv>() : nullptr, c->bvh_top_nodes};
+    SceneDev sc{c->nodes.as<float4>(), c->tris.as<float4>(), c->wnodes.as<float4>(), c->tris.as<float4>(),
+                c->tshade.as<float4>(), c->tclass.as<uint8_t>(),
+                c->mats.as<GMat>(),
+                c->ems.as<GEmitter>(), c->emtri.as<float4>(), c->emcdf.as<float>(),
+                c->has_env ? c->env.as<GEnv>() : nullptr, c->bvh_top_nodes};
+    sc.num_em_boxes = c->num_em_boxes;
+    sc.em_absmax = c->em_absmax;
+    std::memcpy(sc.em_box, c->em_box, sizeof(sc.em_box));
+    return sc;
 }
 SDDev sdView(const Ctx *c) {
     SDDev s{};
@@ -517,7 +529,7 @@ void releasePaths(Ctx *c) {
     for (int li = 0; li < c->nlanes; ++li) {
         Lane &l = c->lanes[li];
         for (DevBuf *b : {&l.ray_o, &l.ray_d, &l.hit, &l.thr, &l.rad, &l.prev, &l.pinfo, &l.sh_d, &l.sh_c,
-                          &l.vtx, &l.q0, &l.q1, &l.qs, &l.class_q, &l.aov, &l.qkey, &l.qsorted})
+                          &l.vtx, &l.q0, &l.q1, &l.qs, &l.qp, &l.class_q, &l.aov, &l.qkey, &l.qsorted})
             b->release();
         l.P = 0;
         l.vtx_slots = 0;
@@ -539,9 +551,10 @@ pg_status ensurePaths(Ctx *c, uint32_t want, bool rec) {
             HIPC(c, hipHostMalloc((void **)&l.h_counts, kCounterWords * 4, hipHostMallocDefault));
             HIPC(c, hipHostMalloc((void **)&l.h_stats, kCounterWords * 4, hipHostMallocDefault));
             HIPC(c, l.counters.alloc(kCounterWords * 4));
-            HIPC(c, l.stack_ovf.alloc(2 * pg_stack_overflow_words(0) * 4));  // k_rays: two launches' worth
-            HIPC(c, l.tail_stats.alloc(32));
-            HIPC(c, hipHostMalloc((void **)&l.h_tail, 32, hipHostMallocDefault));
+            // k_rays: three launches' worth (closest hits, shadow rays, probes)
+            HIPC(c, l.stack_ovf.alloc(3 * pg_stack_overflow_words(0) * 4));
+            HIPC(c, l.tail_stats.alloc(kTailStats * 8));
+            HIPC(c, hipHostMalloc((void **)&l.h_tail, kTailStats * 8, hipHostMallocDefault));
         }
         const bool aovMissing = c->cfg.aovs && !l.aov.p;
         if (vslots > 0 && (vslots > l.vtx_slots || want > l.vtxP)) {
@@ -567,6 +580,7 @@ pg_status ensurePaths(Ctx *c, uint32_t want, bool rec) {
         HIPC(c, l.q0.alloc(qbytes));
         HIPC(c, l.q1.alloc(qbytes));
         HIPC(c, l.qs.alloc(qbytes));
+        HIPC(c, l.qp.alloc(qbytes));
         HIPC(c, l.class_q.alloc((size_t)PG_NUM_CLASSES * qbytes));
         if (c->cfg.aovs) HIPC(c, l.aov.alloc((size_t)P * 16));
         if (raySortEnabled()) {
@@ -950,6 +964,12 @@ pg_status pg_upload_scene(void *ctx, const pg_scene_desc *d) {
         g.inv_area = 1.0f / (float)acc;
         for (int k = 0; k < 4; ++k) g.radiance[k] = pe.radiance[k];
         ems.push_back(g);
+    }
+    {  // padded boxes over the triangles that carry tclass' emitter bit (pg_layout.h "Doom probe")
+        std::vector<uint32_t> triEmitter(nt);
+        for (uint32_t t = 0; t < nt; ++t) triEmitter[t] = triBits[t] >> 16;
+        c->num_em_boxes = pg_emitter_boxes(d->positions, d->indices, triEmitter.data(), nt, d->num_emitters, c->em_box,
+                                           &c->em_absmax);
     }
     c->host_mats.clear();
     for (uint32_t m = 0; m < d->num_materials; ++m) c->host_mats.push_back(makeGMat(d->materials[m]));
@@ -1725,11 +1745,11 @@ static pg_status renderPass(Ctx *c, uint32_t spp, uint32_t sample_offset, int32_
             for (int li = 0; li < c->nlanes; ++li) {
                 const Lane &l = c->lanes[li];
                 for (const DevBuf *b : {&l.ray_o, &l.ray_d, &l.hit, &l.thr, &l.rad, &l.prev, &l.pinfo,
-                                        &l.sh_d, &l.sh_c, &l.vtx, &l.q0, &l.q1, &l.qs, &l.class_q, &l.aov})
+                                        &l.sh_d, &l.sh_c, &l.vtx, &l.q0, &l.q1, &l.qs, &l.qp, &l.class_q, &l.aov})
                     held += b->bytes;
             }
             const int vs = vertexSlots(c, rec);
-            const double perPath = 9.0 * 16 + (3 + PG_NUM_CLASSES) * 4.0 + vs * 16.0 * PG_VTX_F4 + (c->cfg.aovs ? 16.0 : 0.0);
+            const double perPath = 9.0 * 16 + (4 + PG_NUM_CLASSES) * 4.0 + vs * 16.0 * PG_VTX_F4 + (c->cfg.aovs ? 16.0 : 0.0);
             const double fit = 0.7 * (double)(freeB + held) / (perPath * c->nlanes);
             if (fit < (double)cap) cap = std::max<uint32_t>(1u << 20, (uint32_t)fit & ~4095u);
         }
@@ -1787,6 +1807,10 @@ static pg_status renderPass(Ctx *c, uint32_t spp, uint32_t sample_offset, int32_
     // PF_DOOMED (pg_layout.h): roulette and depth exits decided one bounce early, doomed non-emitter hits culled
     // by the tracer; PG_NO_PATH_CULL=1 runs every vertex through the shader as before (same results)
     g.path_cull = std::getenv("PG_NO_PATH_CULL") ? 0 : 1;
+    // doom probe (pg_layout.h): doomed rays that miss every emitter box get an any-hit probe instead of the closest-hit
+    // walk; PG_NO_DOOM_PROBE=1 (or no path cull) traces them all as before (same results).  Never with an environment
+    // emitter: an escaping doomed ray picks up its radiance.
+    g.doom_probe = (g.path_cull && !c->has_env && !std::getenv("PG_NO_DOOM_PROBE")) ? 1 : 0;
     const bool bands = cameraBands() > 0;
     const bool fuseShade = !c->has_env && !std::getenv("PG_NO_SHADE_FUSION");
     // chunks: whole sample layers over the local pixels when they fit, else pixel ranges
@@ -1810,8 +1834,8 @@ static pg_status renderPass(Ctx *c, uint32_t spp, uint32_t sample_offset, int32_
                             cb + kClassCounts + k * PG_QSHARDS);
     };
     // trace of bounce l.b (closest hit + material-class partition), then the class counts to the host;
-    // shq: the previous bounce's shadow queue, traced in the same launch (k_rays)
-    auto launchTrace = [&](Lane &l, const Queue *shq) -> pg_status {
+    // shq, pq: the previous bounce's shadow and probe queues, traced in the same launch (k_rays)
+    auto launchTrace = [&](Lane &l, const Queue *shq, const Queue *pq) -> pg_status {
         uint32_t *cb = l.counters.as<uint32_t>() + (size_t)kBounceWords * l.b;
         Queue cls[PG_CLASS_ROWS];
         classQueues(l, cb, cls);
@@ -1820,7 +1844,7 @@ static pg_status renderPass(Ctx *c, uint32_t spp, uint32_t sample_offset, int32_
         if (evt) HIPC(c, hipEventRecord(et.a, l.stream));
         const Queue tq = lqueue(l, l.sorted ? l.qsorted.as<uint32_t>() : (l.b & 1) ? l.q1.as<uint32_t>() : l.q0.as<uint32_t>(),
                                 cb);
-        if (shq) pg_launch_rays(l.stream, g, sc, pathView(&l), tq, l.bound, cls, *shq, l.bound);
+        if (shq) pg_launch_rays(l.stream, g, sc, pathView(&l), tq, l.bound, cls, *shq, l.bound, *pq);
         else pg_launch_trace(l.stream, g, sc, pathView(&l), tq, l.bound, cls, l.b == 0);
         if (evt) HIPC(c, hipEventRecord(et.b, l.stream));
         HIPC(c, hipMemcpyAsync(l.h_counts + (size_t)kBounceWords * l.b + kClassCounts, cb + kClassCounts,
@@ -1834,11 +1858,15 @@ static pg_status renderPass(Ctx *c, uint32_t spp, uint32_t sample_offset, int32_
         HIPC(c, hipEventSynchronize(l.done));
         for (uint32_t k = 0; k < l.stats_bounces; ++k)
             for (int sh = 0; sh < PG_QSHARDS; ++sh)
+            {
                 c->stats.shadow_rays += l.h_stats[(size_t)kBounceWords * k + kShadowCounts + sh];
+                c->probes += l.h_stats[(size_t)kBounceWords * k + kProbeCounts + sh];
+            }
         c->stats.segments += l.h_tail[0];  // the chunk's tail (k_tail)
         c->stats.escaped += l.h_tail[1];
         c->stats.shadow_rays += l.h_tail[2];
         c->culled += l.h_tail[3];
+        c->probes += l.h_tail[4];
         if (std::getenv("PG_DEBUG_COUNTS")) {
             for (uint32_t k = 0; k < l.stats_bounces && k < l.used_prev.size(); ++k) {
                 uint64_t t = 0;
@@ -1891,10 +1919,10 @@ static pg_status renderPass(Ctx *c, uint32_t spp, uint32_t sample_offset, int32_
         l.chunk = nextChunk++;
         HIPC(c, hipStreamWaitEvent(l.stream, c->pass_start, 0));
         HIPC(c, hipMemsetAsync(l.counters.p, 0, (size_t)kBounceWords * (maxBounces + 1) * 4, l.stream));
-        HIPC(c, hipMemsetAsync(l.tail_stats.p, 0, 32, l.stream));
+        HIPC(c, hipMemsetAsync(l.tail_stats.p, 0, kTailStats * 8, l.stream));
         pg_launch_camera(l.stream, g, pathView(&l), c->d_band_pixels.as<uint32_t>(), l.pb, l.np, l.nl,
                          sample_offset + l.layer0, lqueue(l, l.q0.as<uint32_t>(), l.counters.as<uint32_t>()), bands);
-        return launchTrace(l, nullptr);
+        return launchTrace(l, nullptr, nullptr);
     };
     // film + record commit (in chunk order across lanes), statistics copy; then the next chunk
     auto finishChunk = [&](Lane &l) -> pg_status {
@@ -1902,7 +1930,7 @@ static pg_status renderPass(Ctx *c, uint32_t spp, uint32_t sample_offset, int32_
         if ((st = collectStats(l))) return st;
         const PathDev pv = pathView(&l);
         HIPC(c, hipMemcpyAsync(l.h_stats, l.counters.p, (size_t)kBounceWords * l.b * 4, hipMemcpyDeviceToHost, l.stream));
-        HIPC(c, hipMemcpyAsync(l.h_tail, l.tail_stats.p, 32, hipMemcpyDeviceToHost, l.stream));
+        HIPC(c, hipMemcpyAsync(l.h_tail, l.tail_stats.p, kTailStats * 8, hipMemcpyDeviceToHost, l.stream));
         HIPC(c, hipStreamWaitEvent(l.stream, c->film_order, 0));
         pg_launch_film(l.stream, g, sc, pv, c->d_band_pixels.as<uint32_t>(), l.pb, l.np, l.nl, c->film.as<float4>(),
                        c->film_sq.as<float4>(), c->aov_albedo.as<float4>(), c->aov_normal.as<float4>());
@@ -1991,6 +2019,7 @@ static pg_status renderPass(Ctx *c, uint32_t spp, uint32_t sample_offset, int32_
         const PathDev pv = pathView(&l);
         Queue next = lqueue(l, (l.b & 1) ? l.q1.as<uint32_t>() : l.q0.as<uint32_t>(), cb + kBounceWords);
         const Queue shq = lqueue(l, l.qs.as<uint32_t>(), cb + kShadowCounts);
+        const Queue pq = lqueue(l, l.qp.as<uint32_t>(), cb + kProbeCounts);
         const uint32_t nextBound = *std::max_element(shardLive, shardLive + PG_QSHARDS);
         const bool sortNext = raySortEnabled() && nextBound >= kRaySortMinShard;
         if (sortNext) next.keys = l.qkey.as<uint16_t>();
@@ -1998,11 +2027,11 @@ static pg_status renderPass(Ctx *c, uint32_t spp, uint32_t sample_offset, int32_
         if (evt) es = nextEvents(&l, KT_SHADE);
         if (evt) HIPC(c, hipEventRecord(es.a, l.stream));
         if (fuseShade) {  // one launch for every class present
-            pg_launch_shade_all(l.stream, g, sc, sd, pv, cls, clsMax, next, shq);
+            pg_launch_shade_all(l.stream, g, sc, sd, pv, cls, clsMax, next, shq, pq);
             c->stats.shade_launches += 1;
         } else {
             for (int k = 0; k < PG_NUM_CLASSES; ++k) {
-                pg_launch_shade_class(l.stream, k, g, sc, sd, pv, cls[k], clsMax[k], next, shq);
+                pg_launch_shade_class(l.stream, k, g, sc, sd, pv, cls[k], clsMax[k], next, shq, pq);
                 c->stats.shade_launches += clsMax[k] ? 1 : 0;
             }
         }
@@ -2012,12 +2041,17 @@ static pg_status renderPass(Ctx *c, uint32_t spp, uint32_t sample_offset, int32_
             pg_launch_ray_sort(l.stream, next, l.bound, l.qsorted.as<uint32_t>(), l.rsort_hist.as<uint32_t>());
         l.sorted = sortNext;
         // without per-launch timing the shadow rays share the next trace's launch
-        if (fuseRays) return launchTrace(l, &shq);
+        if (fuseRays) return launchTrace(l, &shq, &pq);
         if (evt) ew = nextEvents(&l, KT_SHADOW);
         if (evt) HIPC(c, hipEventRecord(ew.a, l.stream));
         pg_launch_shadow(l.stream, sc, pv, shq, l.bound);
+        if (g.doom_probe) {  // the probes of this bounce, counted with the closest hits of the trace that follows
+            Queue ncls[PG_CLASS_ROWS];
+            classQueues(l, cb + kBounceWords, ncls);
+            pg_launch_probe(l.stream, sc, pv, pq, l.bound, ncls);
+        }
         if (evt) HIPC(c, hipEventRecord(ew.b, l.stream));
-        return launchTrace(l, nullptr);
+        return launchTrace(l, nullptr, nullptr);
     };
 
     for (int li = 0; li < c->nlanes; ++li)
@@ -2476,6 +2510,12 @@ pg_status pg_get_stats(void *ctx, pg_stats *st) {
     return PG_OK;
 }
 
+pg_status pg_get_probes(void *ctx, uint64_t *count) {
+    Ctx *c = (Ctx *)ctx;
+    if (!c || !count) return fail(c, PG_ERR_INVALID, "pg_get_probes: null argument");
+    *count = c->probes;
+    return PG_OK;
+}
 pg_status pg_get_culled(void *ctx, uint64_t *count) {
     Ctx *c = (Ctx *)ctx;
     if (!c || !count) return fail(c, PG_ERR_INVALID, "pg_get_culled: null argument");

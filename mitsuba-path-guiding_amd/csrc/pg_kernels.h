@@ -18,6 +18,10 @@ struct SceneDev {
     const float *emcdf;
     const GEnv *env;        // environment emitter (the last emitter), or nullptr
     uint32_t top_nodes;     // binary-BVH nodes [0, top_nodes) are the top levels (k_trace stages them in LDS)
+    // padded boxes over the emitter triangles (pg_layout.h "Doom probe"; by value, so they sit in scalar registers)
+    uint32_t num_em_boxes;
+    float em_absmax;        // the boxes' largest |coordinate|
+    float em_box[PG_EMBOX_MAX][6];
 };
 
 // float4 per training vertex: (x, woPdf), (T after the vertex, packed canonical wo), (L snapshot, -),
@@ -162,19 +166,24 @@ void pg_launch_camera(hipStream_t s, const GParams &g, const PathDev &p, const u
 // first_bounce: the chunk's camera rays (their hit records are kept in p.aov when it is set)
 void pg_launch_trace(hipStream_t s, const GParams &g, const SceneDev &sc, const PathDev &p, Queue q, uint32_t max_shard,
                      const Queue *class_queues, bool first_bounce);
+// probe: the doomed rays that miss every emitter box (pg_layout.h "Doom probe"), answered by pg_launch_rays / _probe
 void pg_launch_shade_class(hipStream_t s, int cls, const GParams &g, const SceneDev &sc, const SDDev &sd,
-                           const PathDev &p, Queue in, uint32_t max_shard, Queue out, Queue shadow);
+                           const PathDev &p, Queue in, uint32_t max_shard, Queue out, Queue shadow, Queue probe);
 // every material class of a bounce in one launch (k_shade_all; scenes without an environment
 // emitter): pg_launch_shade_class for each class c with max_shard[c] > 0
 void pg_launch_shade_all(hipStream_t s, const GParams &g, const SceneDev &sc, const SDDev &sd, const PathDev &p,
-                         const Queue *class_queues, const uint32_t *max_shard, Queue out, Queue shq);
+                         const Queue *class_queues, const uint32_t *max_shard, Queue out, Queue shq, Queue probe);
 // shadow rays of a bounce and the closest hits of the next in one launch (k_rays; scenes without an
-// environment emitter): the pair pg_launch_shadow + pg_launch_trace without the aov hook
+// environment emitter): the pair pg_launch_shadow + pg_launch_trace without the aov hook, and the any-hit probes of
+// `probe` (max_shadow_shard bounds its shards too), counted in class_queues' culled / escaped rows
 void pg_launch_rays(hipStream_t s, const GParams &g, const SceneDev &sc, const PathDev &p, Queue q, uint32_t max_shard,
-                    const Queue *class_queues, Queue shq, uint32_t max_shadow_shard);
+                    const Queue *class_queues, Queue shq, uint32_t max_shadow_shard, Queue probe);
 void pg_launch_shadow(hipStream_t s, const SceneDev &sc, const PathDev &p, Queue q, uint32_t max_shard);
+// the probes alone (the unfused launches): hits to class_queues[PG_CLASS_CULLED], misses to [PG_CLASS_ESCAPED]
+void pg_launch_probe(hipStream_t s, const SceneDev &sc, const PathDev &p, Queue probe, uint32_t max_shard,
+                     const Queue *class_queues);
 // every remaining path of the queue `q` (its hits already traced) to its end in one launch, each thread
-// looping shade -> shadow ray -> closest hit (k_tail); stats: 3 u64 (segments, escaped, shadow rays)
+// looping shade -> shadow ray -> closest hit (k_tail); stats: 5 u64 (segments, escaped, shadow rays, culled, probes)
 void pg_launch_tail(hipStream_t s, const GParams &g, const SceneDev &sc, const SDDev &sd, const PathDev &p, Queue q,
                     uint32_t max_shard, unsigned long long *stats);
 // counting sort of every shard of `q` by its keys into sorted_items (same shard layout and counts):

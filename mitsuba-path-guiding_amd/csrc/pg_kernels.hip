@@ -400,10 +400,51 @@ __global__ __launch_bounds__(TRACE_BLOCK) void k_shadow(SceneDev sc, PathDev p, 
     shadowRows(sc, p, q, blockIdx.x, gridDim.x, threadWideStack(stack, p.stack_ovf));
 }
 
+// Doom probe (pg_layout.h): does the doomed ray (o, d) hit anything?  The closest-hit walk's own 4-wide nodes, padded
+// box tests, tmin and TriAccel records with tmax = inf, stopped at the first accepted triangle.  Until its first
+// accepted triangle a closest-hit walk visits the same nodes and leaves in the same order (its culling distance is
+// still inf), so "hit" here is exactly "the closest-hit walk would have returned a hit".  (The shadow rays' 8-wide
+// tree culls boxes differently and could disagree on a grazing ray.)
+__device__ __forceinline__ bool probeHit(const SceneDev &sc, float4 o, float4 d, const TStack &stk) {
+    float tmax = __builtin_huge_valf(), u = 0, v = 0;
+    uint32_t tri = 0xFFFFFFFFu;
+    return traverse<true>(sc.nodes, sc.tris, xyz(o), xyz(d), fabsf(o.w), tmax, tri, u, v, stk);
+}
+// the probes of queue shard bid % PG_QSHARDS that block bid of nblk takes (a grid-stride loop as shadowRows'): no hit
+// record, no class queue; a wave adds its hits to the culled row and its misses to the escaped row of the counter
+// block the same launch's closest hits use, so the host's accounting sees them as it did when they were traced
+__device__ __forceinline__ void probeRows(const SceneDev &sc, const PathDev &p, const Queue &q, const ClassQueues &cqs,
+                                          uint32_t bid, uint32_t nblk, const TStack &stk) {
+    const uint32_t s = bid & (PG_QSHARDS - 1);
+    const uint32_t n = q.counts[s];
+    const uint32_t *items = q.items + (size_t)s * q.stride;
+    uint32_t hits = 0, misses = 0;
+    for (uint32_t i = (bid / PG_QSHARDS) * TRACE_BLOCK + threadIdx.x; i < n; i += nblk / PG_QSHARDS * TRACE_BLOCK) {
+        const uint32_t slot = items[i];
+        if (probeHit(sc, ldS(&p.ray_o[slot]), ldS(&p.ray_d[slot]), stk)) ++hits;
+        else ++misses;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        hits += __shfl_xor(hits, off);
+        misses += __shfl_xor(misses, off);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (hits) atomicAdd(cqs.q[PG_CLASS_CULLED].counts + s, hits);
+        if (misses) atomicAdd(cqs.q[PG_CLASS_ESCAPED].counts + s, misses);
+    }
+}
+// the probes in a launch of their own (the unfused launches, PG_NO_RAYS_FUSION)
+__global__ __launch_bounds__(TRACE_BLOCK) void k_probe(SceneDev sc, PathDev p, Queue q, ClassQueues cqs) {
+    __shared__ uint32_t stack[LDS_STACK * TRACE_BLOCK];
+    probeRows(sc, p, q, cqs, blockIdx.x, gridDim.x, threadStack(stack, p.stack_ovf));
+}
+
 // a bounce's shadow rays and the next closest hits in one launch: blocks [0, shadow_blocks) run
 // k_shadow's rows, the rest k_trace's (an escaped path's environment radiance goes to its hit
-// record, not to L, so it cannot race with the same path's NEE add).  Both parts are grid-stride loops over their shards; the
-// overflow ring holds two launches' worth of threads (2 x pg_stack_overflow_words(0)).
+// record, not to L, so it cannot race with the same path's NEE add).  Blocks past those two ranges run the doom probes
+// (probeRows) of the bounce just shaded: rays of paths that are in neither of the other queues' next vertices, and
+// blocks of their own, so they do not lengthen the closest-hit waves.  All parts are grid-stride loops over their
+// shards; the overflow ring holds three launches' worth of threads (3 x pg_stack_overflow_words(0)).
 static_assert(2 * WIDE_LDS_STACK >= LDS_STACK, "k_rays / k_trace_rays share one LDS stack array");
 #ifndef PG_RAYS_TRACE_FIRST
 #define PG_RAYS_TRACE_FIRST 1
@@ -413,11 +454,16 @@ template <bool ENV>
 #define PG_RAYS_WAVES 8
 #endif
 __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PG_RAYS_WAVES))) void k_rays(GParams g, SceneDev sc, PathDev p, Queue q, ClassQueues cqs,
-                                                      Queue shq, uint32_t shadow_blocks) {
+                                                      Queue shq, uint32_t shadow_blocks, Queue pq, uint32_t probe_blocks) {
     // >= LDS_STACK words per thread (twice that for the paired walks)
     __shared__ uint32_t stack[(PG_TRACE_PAIR ? 2 : 1) * 2 * WIDE_LDS_STACK * TRACE_BLOCK];
+    // the probe blocks come last in either order
+    if (blockIdx.x >= gridDim.x - probe_blocks) {
+        probeRows(sc, p, pq, cqs, blockIdx.x - (gridDim.x - probe_blocks), probe_blocks, threadStack(stack, p.stack_ovf));
+        return;
+    }
 #if PG_RAYS_TRACE_FIRST  // the costlier closest-hit blocks dispatched first (profiles/r03zg_rays_order_ab)
-    const uint32_t trace_blocks = gridDim.x - shadow_blocks;
+    const uint32_t trace_blocks = gridDim.x - probe_blocks - shadow_blocks;
     if (blockIdx.x >= trace_blocks) {
         shadowRows(sc, p, shq, blockIdx.x - trace_blocks, shadow_blocks, threadWideStack(stack, p.stack_ovf));
     } else {
@@ -443,8 +489,8 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PG_
     if (blockIdx.x < shadow_blocks)
         shadowRows(sc, p, shq, blockIdx.x, shadow_blocks, threadWideStack(stack, p.stack_ovf));
     else
-        traceRows<ENV, false>(g, sc, p, q, cqs, nullptr, blockIdx.x - shadow_blocks, gridDim.x - shadow_blocks,
-                                threadStack(stack, p.stack_ovf), nullptr, 0);
+        traceRows<ENV, false>(g, sc, p, q, cqs, nullptr, blockIdx.x - shadow_blocks,
+                              gridDim.x - probe_blocks - shadow_blocks, threadStack(stack, p.stack_ovf), nullptr, 0);
 #endif
 }
 
@@ -531,7 +577,7 @@ extern "C" int pg_debug_watch_read(float *out, uint32_t max, uint32_t *n) {
 template <int MODEL, bool CAN_GUIDE, bool ENV>
 __device__ __forceinline__ void shadeOne(const GParams &g, const SceneDev &sc, const SDDev &sd, const PathDev &p,
                                          uint32_t slot, const GMat *mats, bool wantKey, bool &alive, bool &shadow,
-                                         uint32_t &rkey) {
+                                         bool &probe, uint32_t &rkey) {
     bool dirtyL = false;
     f3 L = mk1(0.f);
     // the watch build logs every vertex with its own roulette draw, as the oracle does
@@ -790,19 +836,29 @@ __device__ __forceinline__ void shadeOne(const GParams &g, const SceneDev &sc, c
                     doomed = D > g.depth_cap || (g.max_depth > 0 && (int)D >= g.max_depth) ||
                              (D - 1 >= (uint32_t)g.rr_depth && rrNext >= fminf(maxc(Tn) * etaN * etaN, 0.95f));
                 }
+                // doom probe (pg_layout.h): a doomed ray that misses every emitter box cannot end on an emitter, so
+                // only whether it hits anything is still wanted (culled against escaped)
+                if (!ENV && doomed && g.doom_probe) {
+                    const float po[3] = {h.p.x, h.p.y, h.p.z}, pd[3] = {wo.x, wo.y, wo.z};
+                    probe = pg_ray_misses_boxes(sc.em_box, sc.num_em_boxes, sc.em_absmax, po, pd, tmin);
+                }
                 stS(&p.ray_o[slot], f4(h.p, doomed ? -tmin : tmin));
                 stS(&p.ray_d[slot], f4(wo, __int_as_float(0x7f800000)));
-                stS(&p.thr[slot], f4(Tn, etaN));
-                stS(&p.prev[slot], f4(refN, woPdf));
-                flags = (flags & ~(PF_EMITTED_QUERY | PF_PREV_DELTA)) | ((bs.type & EDelta) ? PF_PREV_DELTA : 0u) |
-                        (doomed ? PF_DOOMED : 0u);
-                stPinfoZW(&p.pinfo[slot], (depth + 1) | (flags << 16), nv);
-                alive = true;
-                if (wantKey) rkey = rayOrderKey(sd, h.p, wo);
+                if (probe) {  // the path ends here: the hit record a culled hit gets, no state for a next vertex
+                    stS(&p.hit[slot], make_float4(0.0f, __uint_as_float(0xFFFFFFFFu), 0.0f, 0.0f));
+                } else {
+                    stS(&p.thr[slot], f4(Tn, etaN));
+                    stS(&p.prev[slot], f4(refN, woPdf));
+                    flags = (flags & ~(PF_EMITTED_QUERY | PF_PREV_DELTA)) | ((bs.type & EDelta) ? PF_PREV_DELTA : 0u) |
+                            (doomed ? PF_DOOMED : 0u);
+                    stPinfoZW(&p.pinfo[slot], (depth + 1) | (flags << 16), nv);
+                    alive = true;
+                    if (wantKey) rkey = rayOrderKey(sd, h.p, wo);
+                }
             }
         }
         if (shadow) {  // origin: ray_o (the extension ray's, written above when the path goes on)
-            if (!alive) stS(&p.ray_o[slot], f4(h.p, 0.0f));
+            if (!alive && !probe) stS(&p.ray_o[slot], f4(h.p, 0.0f));
             stS(&p.sh_d[slot], f4(neeD, neeDist * (1 - kShadowEpsilon)));
             stS(&p.sh_c[slot], f4(neeC, __uint_as_float(vtxIndex)));
         }
@@ -822,7 +878,8 @@ __device__ __forceinline__ void shadeOne(const GParams &g, const SceneDev &sc, c
 
 template <int MODEL, bool CAN_GUIDE, bool ENV>
 __device__ __forceinline__ void shadeBlock(const GParams &g, const SceneDev &sc, const SDDev &sd, const PathDev &p,
-                                           const Queue &in, const Queue &out, const Queue &shq, uint32_t bid) {
+                                           const Queue &in, const Queue &out, const Queue &shq, const Queue &pq,
+                                           uint32_t bid) {
     // one item per thread (a grid-stride loop here cost ~45 VGPRs of hoisted invariants): block b
     // takes row b / PG_QSHARDS of shard b % PG_QSHARDS; rows past the shard's count exit at once
     const uint32_t s = bid & (PG_QSHARDS - 1);
@@ -831,7 +888,7 @@ __device__ __forceinline__ void shadeBlock(const GParams &g, const SceneDev &sc,
     const uint32_t base = (bid / PG_QSHARDS) * SHADE_BLOCK;
     if (base >= n) return;
     const uint32_t i = base + threadIdx.x;
-    bool alive = false, shadow = false;
+    bool alive = false, shadow = false, probe = false;
     uint32_t slot = 0, rkey = 0;
     if (i < n) slot = in.items[(size_t)s * in.stride + i];
     // the material table, staged in LDS once per block (the material read sits on the dependent chain
@@ -845,20 +902,22 @@ __device__ __forceinline__ void shadeBlock(const GParams &g, const SceneDev &sc,
     }
     if (i < n)
         shadeOne<MODEL, CAN_GUIDE, ENV>(g, sc, sd, p, slot, ldsMats ? reinterpret_cast<const GMat *>(smat) : sc.mats,
-                                        out.keys != nullptr, alive, shadow, rkey);
+                                        out.keys != nullptr, alive, shadow, probe, rkey);
     if (out.keys)
         waveAppendKey(alive, slot, (uint16_t)rkey, out.items + (size_t)s * out.stride, out.keys + (size_t)s * out.stride,
                       out.counts + s);
     else
         waveAppend(alive, slot, out.items + (size_t)s * out.stride, out.counts + s);
     waveAppend(shadow, slot, shq.items + (size_t)s * shq.stride, shq.counts + s);
+    // doomed rays that miss every emitter box: the tracer's probe rows (never set with ENV or without the probe)
+    if (!ENV && g.doom_probe) waveAppend(probe, slot, pq.items + (size_t)s * pq.stride, pq.counts + s);
     }
 }
 
 template <int MODEL, bool CAN_GUIDE, bool ENV>
 __global__ __launch_bounds__(SHADE_BLOCK) void k_shade(GParams g, SceneDev sc, SDDev sd, PathDev p, Queue in,
-                                                       Queue out, Queue shq) {
-    shadeBlock<MODEL, CAN_GUIDE, ENV>(g, sc, sd, p, in, out, shq, blockIdx.x);
+                                                       Queue out, Queue shq, Queue pq) {
+    shadeBlock<MODEL, CAN_GUIDE, ENV>(g, sc, sd, p, in, out, shq, pq, blockIdx.x);
 }
 
 // every material class of a bounce in one launch (no environment emitter): blocks
@@ -871,15 +930,15 @@ struct ShadeRanges {
 #define PG_SHADE_WAVES 4
 #endif
 __global__ __launch_bounds__(SHADE_BLOCK) __attribute__((amdgpu_waves_per_eu(PG_SHADE_WAVES))) void k_shade_all(
-    GParams g, SceneDev sc, SDDev sd, PathDev p, ClassQueues in, Queue out, Queue shq, ShadeRanges r) {
+    GParams g, SceneDev sc, SDDev sd, PathDev p, ClassQueues in, Queue out, Queue shq, Queue pq, ShadeRanges r) {
     static_assert(PG_NUM_CLASSES == 6, "class ranges");
     const uint32_t b = blockIdx.x;
-    if (b < r.end[0]) shadeBlock<PG_BSDF_DIFFUSE, true, false>(g, sc, sd, p, in.q[0], out, shq, b);
-    else if (b < r.end[1]) shadeBlock<PG_BSDF_ROUGHCONDUCTOR, true, false>(g, sc, sd, p, in.q[1], out, shq, b - r.end[0]);
-    else if (b < r.end[2]) shadeBlock<PG_BSDF_ROUGHDIELECTRIC, true, false>(g, sc, sd, p, in.q[2], out, shq, b - r.end[1]);
-    else if (b < r.end[3]) shadeBlock<PG_BSDF_PLASTIC, false, false>(g, sc, sd, p, in.q[3], out, shq, b - r.end[2]);
-    else if (b < r.end[4]) shadeBlock<PG_BSDF_ROUGHPLASTIC, true, false>(g, sc, sd, p, in.q[4], out, shq, b - r.end[3]);
-    else shadeBlock<-1, false, false>(g, sc, sd, p, in.q[5], out, shq, b - r.end[4]);
+    if (b < r.end[0]) shadeBlock<PG_BSDF_DIFFUSE, true, false>(g, sc, sd, p, in.q[0], out, shq, pq, b);
+    else if (b < r.end[1]) shadeBlock<PG_BSDF_ROUGHCONDUCTOR, true, false>(g, sc, sd, p, in.q[1], out, shq, pq, b - r.end[0]);
+    else if (b < r.end[2]) shadeBlock<PG_BSDF_ROUGHDIELECTRIC, true, false>(g, sc, sd, p, in.q[2], out, shq, pq, b - r.end[1]);
+    else if (b < r.end[3]) shadeBlock<PG_BSDF_PLASTIC, false, false>(g, sc, sd, p, in.q[3], out, shq, pq, b - r.end[2]);
+    else if (b < r.end[4]) shadeBlock<PG_BSDF_ROUGHPLASTIC, true, false>(g, sc, sd, p, in.q[4], out, shq, pq, b - r.end[3]);
+    else shadeBlock<-1, false, false>(g, sc, sd, p, in.q[5], out, shq, pq, b - r.end[4]);
 }
 
 // ---- counting sort of a queue's shards by ray order key (PG_RAY_SORT): the next closest-hit launch
@@ -966,24 +1025,25 @@ __global__ __launch_bounds__(256) void k_rsort_scatter(Queue q, uint32_t *hist, 
 // wavefront's own code on the path's own state and random numbers, in the same order (a path's NEE
 // is added before its next vertex is shaded), so films, records and trees are bit-identical with
 // the bounce-by-bounce loop.  Input: the queue of the bounce just traced (hits already in p.hit).
-// stats: [0] traced segments, [1] escaped segments, [2] shadow rays, [3] culled hits (u64, device atomics).
+// stats: [0] traced segments, [1] escaped segments, [2] shadow rays, [3] culled hits, [4] probed segments (u64,
+// device atomics; a probe is also a segment and either a culled hit or an escape).
 template <bool ENV>
 __device__ __forceinline__ void tailShade(const GParams &g, const SceneDev &sc, const SDDev &sd, const PathDev &p,
-                                          uint32_t slot, uint32_t tri, bool &alive, bool &shadow) {
+                                          uint32_t slot, uint32_t tri, bool &alive, bool &shadow, bool &probe) {
     uint32_t rk = 0;
     switch (sc.tclass[tri] & PG_TCLASS_MASK) {
-        case PG_CLASS_DIFFUSE: shadeOne<PG_BSDF_DIFFUSE, true, ENV>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, rk); break;
+        case PG_CLASS_DIFFUSE: shadeOne<PG_BSDF_DIFFUSE, true, ENV>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, probe, rk); break;
         case PG_CLASS_ROUGHCONDUCTOR:
-            shadeOne<PG_BSDF_ROUGHCONDUCTOR, true, ENV>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, rk);
+            shadeOne<PG_BSDF_ROUGHCONDUCTOR, true, ENV>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, probe, rk);
             break;
         case PG_CLASS_ROUGHDIELECTRIC:
-            shadeOne<PG_BSDF_ROUGHDIELECTRIC, true, ENV>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, rk);
+            shadeOne<PG_BSDF_ROUGHDIELECTRIC, true, ENV>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, probe, rk);
             break;
-        case PG_CLASS_PLASTIC: shadeOne<PG_BSDF_PLASTIC, false, ENV>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, rk); break;
+        case PG_CLASS_PLASTIC: shadeOne<PG_BSDF_PLASTIC, false, ENV>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, probe, rk); break;
         case PG_CLASS_ROUGHPLASTIC:
-            shadeOne<PG_BSDF_ROUGHPLASTIC, true, ENV>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, rk);
+            shadeOne<PG_BSDF_ROUGHPLASTIC, true, ENV>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, probe, rk);
             break;
-        default: shadeOne<-1, false, ENV>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, rk);
+        default: shadeOne<-1, false, ENV>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, probe, rk);
     }
 }
 template <bool ENV>
@@ -998,13 +1058,13 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PG_
     const uint32_t s = blockIdx.x & (PG_QSHARDS - 1);
     const uint32_t rows = gridDim.x / PG_QSHARDS;  // grid capped at TRACE_MAX_BLOCKS: the overflow ring's size
     const uint32_t n = q.counts[s];
-    uint32_t segs = 0, esc = 0, shadows = 0, culled = 0;
+    uint32_t segs = 0, esc = 0, shadows = 0, culled = 0, probes = 0;
     for (uint32_t i = (blockIdx.x / PG_QSHARDS) * TRACE_BLOCK + threadIdx.x; i < n; i += rows * TRACE_BLOCK) {
         const uint32_t slot = q.items[(size_t)s * q.stride + i];
         uint32_t tri = __float_as_uint(ldS(&p.hit[slot]).y);
         while (tri != 0xFFFFFFFFu) {
-            bool alive = false, shadow = false;
-            tailShade<ENV>(g, sc, sd, p, slot, tri, alive, shadow);
+            bool alive = false, shadow = false, probe = false;
+            tailShade<ENV>(g, sc, sd, p, slot, tri, alive, shadow, probe);
             if (shadow) {  // shadowRows for this path
                 ++shadows;
                 const float4 o = ldS(&p.ray_o[slot]), d = ldS(&p.sh_d[slot]);
@@ -1019,6 +1079,13 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PG_
                         *vl = make_float4(a.x + c.x, a.y + c.y, a.z + c.z, a.w);
                     }
                 }
+            }
+            if (!ENV && probe) {  // probeRows for this path: its last segment, a culled hit or an escape
+                const float4 o = ldS(&p.ray_o[slot]), d = ldS(&p.ray_d[slot]);
+                ++segs;
+                ++probes;
+                if (probeHit(sc, o, d, stk)) ++culled;
+                else ++esc;
             }
             if (!alive) break;
             // traceRows for this path
@@ -1040,18 +1107,20 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PG_
         }
     }
     // wave-summed counters
-    unsigned long long a = segs, b = esc, c = shadows, e = culled;
+    unsigned long long a = segs, b = esc, c = shadows, e = culled, f = probes;
     for (int off = 32; off > 0; off >>= 1) {
         a += __shfl_xor(a, off);
         b += __shfl_xor(b, off);
         c += __shfl_xor(c, off);
         e += __shfl_xor(e, off);
+        f += __shfl_xor(f, off);
     }
     if ((threadIdx.x & 63) == 0 && (a | b | c)) {
         atomicAdd(stats + 0, a);
         atomicAdd(stats + 1, b);
         atomicAdd(stats + 2, c);
         if (e) atomicAdd(stats + 3, e);
+        if (f) atomicAdd(stats + 4, f);
     }
 }
 
@@ -1506,37 +1575,37 @@ void pg_launch_trace(hipStream_t s, const GParams &g, const SceneDev &sc, const 
 }
 template <bool ENV>
 static void launchShade(hipStream_t s, int cls, dim3 grid, const GParams &g, const SceneDev &sc, const SDDev &sd,
-                        const PathDev &p, Queue in, Queue out, Queue shq) {
+                        const PathDev &p, Queue in, Queue out, Queue shq, Queue pq) {
     const dim3 block(SHADE_BLOCK);
     switch (cls) {
         case PG_CLASS_DIFFUSE:
-            hipLaunchKernelGGL((k_shade<PG_BSDF_DIFFUSE, true, ENV>), grid, block, 0, s, g, sc, sd, p, in, out, shq);
+            hipLaunchKernelGGL((k_shade<PG_BSDF_DIFFUSE, true, ENV>), grid, block, 0, s, g, sc, sd, p, in, out, shq, pq);
             break;
         case PG_CLASS_ROUGHCONDUCTOR:
-            hipLaunchKernelGGL((k_shade<PG_BSDF_ROUGHCONDUCTOR, true, ENV>), grid, block, 0, s, g, sc, sd, p, in, out, shq);
+            hipLaunchKernelGGL((k_shade<PG_BSDF_ROUGHCONDUCTOR, true, ENV>), grid, block, 0, s, g, sc, sd, p, in, out, shq, pq);
             break;
         case PG_CLASS_ROUGHDIELECTRIC:
-            hipLaunchKernelGGL((k_shade<PG_BSDF_ROUGHDIELECTRIC, true, ENV>), grid, block, 0, s, g, sc, sd, p, in, out, shq);
+            hipLaunchKernelGGL((k_shade<PG_BSDF_ROUGHDIELECTRIC, true, ENV>), grid, block, 0, s, g, sc, sd, p, in, out, shq, pq);
             break;
         case PG_CLASS_PLASTIC:
-            hipLaunchKernelGGL((k_shade<PG_BSDF_PLASTIC, false, ENV>), grid, block, 0, s, g, sc, sd, p, in, out, shq);
+            hipLaunchKernelGGL((k_shade<PG_BSDF_PLASTIC, false, ENV>), grid, block, 0, s, g, sc, sd, p, in, out, shq, pq);
             break;
         case PG_CLASS_ROUGHPLASTIC:
-            hipLaunchKernelGGL((k_shade<PG_BSDF_ROUGHPLASTIC, true, ENV>), grid, block, 0, s, g, sc, sd, p, in, out, shq);
+            hipLaunchKernelGGL((k_shade<PG_BSDF_ROUGHPLASTIC, true, ENV>), grid, block, 0, s, g, sc, sd, p, in, out, shq, pq);
             break;
         default:  // delta lobes: conductor, dielectric (runtime switch, never guided)
-            hipLaunchKernelGGL((k_shade<-1, false, ENV>), grid, block, 0, s, g, sc, sd, p, in, out, shq);
+            hipLaunchKernelGGL((k_shade<-1, false, ENV>), grid, block, 0, s, g, sc, sd, p, in, out, shq, pq);
     }
 }
 void pg_launch_shade_class(hipStream_t s, int cls, const GParams &g, const SceneDev &sc, const SDDev &sd,
-                           const PathDev &p, Queue in, uint32_t max_shard, Queue out, Queue shq) {
+                           const PathDev &p, Queue in, uint32_t max_shard, Queue out, Queue shq, Queue pq) {
     if (!max_shard) return;
     const dim3 grid = shardGrid(max_shard, SHADE_BLOCK, 0xFFFFFFFFu);
-    if (sc.env) launchShade<true>(s, cls, grid, g, sc, sd, p, in, out, shq);
-    else launchShade<false>(s, cls, grid, g, sc, sd, p, in, out, shq);
+    if (sc.env) launchShade<true>(s, cls, grid, g, sc, sd, p, in, out, shq, pq);
+    else launchShade<false>(s, cls, grid, g, sc, sd, p, in, out, shq, pq);
 }
 void pg_launch_shade_all(hipStream_t s, const GParams &g, const SceneDev &sc, const SDDev &sd, const PathDev &p,
-                         const Queue *class_queues, const uint32_t *max_shard, Queue out, Queue shq) {
+                         const Queue *class_queues, const uint32_t *max_shard, Queue out, Queue shq, Queue pq) {
     ClassQueues cq;
     ShadeRanges r;
     uint32_t total = 0;
@@ -1547,22 +1616,34 @@ void pg_launch_shade_all(hipStream_t s, const GParams &g, const SceneDev &sc, co
     }
     for (int c = PG_NUM_CLASSES; c < PG_CLASS_ROWS; ++c) cq.q[c] = class_queues[c];
     if (!total) return;
-    hipLaunchKernelGGL(k_shade_all, dim3(total), dim3(SHADE_BLOCK), 0, s, g, sc, sd, p, cq, out, shq, r);
+    hipLaunchKernelGGL(k_shade_all, dim3(total), dim3(SHADE_BLOCK), 0, s, g, sc, sd, p, cq, out, shq, pq, r);
 }
 void pg_launch_rays(hipStream_t s, const GParams &g, const SceneDev &sc, const PathDev &p, Queue q, uint32_t max_shard,
-                    const Queue *class_queues, Queue shq, uint32_t max_shadow_shard) {
+                    const Queue *class_queues, Queue shq, uint32_t max_shadow_shard, Queue pq) {
     ClassQueues cq;
     for (int c = 0; c < PG_CLASS_ROWS; ++c) cq.q[c] = class_queues[c];
     const uint32_t sb = max_shadow_shard ? shardGrid(max_shadow_shard, TRACE_BLOCK, TRACE_MAX_BLOCKS / PG_QSHARDS).x : 0;
+    // the probe queue's shards are bounded as the shadow queue's (both hold vertices of the bounce just shaded)
+    const uint32_t pb = (g.doom_probe && !sc.env) ? sb : 0;
     const uint32_t tb =
         max_shard ? shardGrid(max_shard, (PG_TRACE_PAIR ? 2 : 1) * TRACE_BLOCK, TRACE_MAX_BLOCKS / PG_QSHARDS).x : 0;
     if (sb + tb == 0) return;
     if (tb == 0) {  // no trace rows: k_rays needs at least one trace block per shard to stay sharded
         hipLaunchKernelGGL(k_shadow, dim3(sb), dim3(TRACE_BLOCK), 0, s, sc, p, shq);
+        if (pb) hipLaunchKernelGGL(k_probe, dim3(pb), dim3(TRACE_BLOCK), 0, s, sc, p, pq, cq);
         return;
     }
-    if (sc.env) hipLaunchKernelGGL(k_rays<true>, dim3(sb + tb), dim3(TRACE_BLOCK), 0, s, g, sc, p, q, cq, shq, sb);
-    else hipLaunchKernelGGL(k_rays<false>, dim3(sb + tb), dim3(TRACE_BLOCK), 0, s, g, sc, p, q, cq, shq, sb);
+    // sb + tb + pb <= 3 TRACE_MAX_BLOCKS: the overflow ring's size (pg_host.cpp ensurePaths)
+    if (sc.env) hipLaunchKernelGGL(k_rays<true>, dim3(sb + tb + pb), dim3(TRACE_BLOCK), 0, s, g, sc, p, q, cq, shq, sb, pq, pb);
+    else hipLaunchKernelGGL(k_rays<false>, dim3(sb + tb + pb), dim3(TRACE_BLOCK), 0, s, g, sc, p, q, cq, shq, sb, pq, pb);
+}
+void pg_launch_probe(hipStream_t s, const SceneDev &sc, const PathDev &p, Queue pq, uint32_t max_shard,
+                     const Queue *class_queues) {
+    if (!max_shard) return;
+    ClassQueues cq;
+    for (int c = 0; c < PG_CLASS_ROWS; ++c) cq.q[c] = class_queues[c];
+    hipLaunchKernelGGL(k_probe, shardGrid(max_shard, TRACE_BLOCK, TRACE_MAX_BLOCKS / PG_QSHARDS), dim3(TRACE_BLOCK), 0, s,
+                       sc, p, pq, cq);
 }
 void pg_launch_shadow(hipStream_t s, const SceneDev &sc, const PathDev &p, Queue q, uint32_t max_shard) {
     if (!max_shard) return;

@@ -1,6 +1,8 @@
 // GPU record layouts shared by the host driver (pg_host.cpp) and the kernels (pg_kernels.hip).
 // Sizes are static_asserted; DESIGN.md §"Data layout in HBM" documents them.
 #pragma once
+#include <math.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/pg_capi.h"
@@ -263,9 +265,91 @@ inline void pg_qnode_box(const float *node, int s, float lo[3], float hi[3]) {
 //     that hits a non-emitter is culled by the tracer: its hit record is stored as a miss (0, ~0, 0, 0), it joins
 //     no class queue and is counted in the PG_CLASS_CULLED row;
 //   - a doomed ray that hits an emitter is shaded: shadeOne adds the MIS-weighted emission, sees PF_DOOMED and
-//     stops where the roulette draw used to be.
+//     stops where the roulette draw used to be;
+//   - without an environment emitter, a doomed ray that misses every emitter box is not traced at all ("Doom probe"
+//     below): its path ends in the shader and an any-hit probe decides culled against escaped.
 // Set only while GParams::path_cull is on; then a vertex without the flag has survived its roulette.
 #define PF_DOOMED 0x8u
+
+// Doom probe: emitter bounds (SceneDev::em_box, scenes without an environment emitter).  A doomed ray matters only
+// if its closest hit is an emitter triangle, so shadeOne slab-tests it against up to PG_EMBOX_MAX axis-aligned boxes
+// over the emitter triangles (one per emitter, or their union beyond PG_EMBOX_MAX).  A ray that misses every box
+// cannot end on an emitter: it is not queued for the closest-hit walk, and an any-hit probe of the same 4-wide
+// nodes only decides `culled` against `escaped` (pg_kernels.hip probeRows).
+// Why the test never rejects a ray the walk could return an emitter for: TriAccel accepts a hit at its fp32 t >=
+// tmin when the ray's point at t projects into the triangle, up to the rounding of (o + t d), and the plane solve
+// leaves that point off the triangle's plane by at most ~100 ulps of max(|o|, |vertex|) (grazing
+// rays far from the origin).  So the exact ray passes within ~6e-6 max(|o|, |vertex|) of the triangle at some
+// t >= tmin.  Every box is padded on all sides by 1e-3 of its largest extent plus 1e-3 of its largest absolute
+// coordinate (160 times that bound for an origin no farther out than the box), and the slab test widens every
+// interval by 2^-16 (max|o| + the boxes' largest |coordinate|) along each axis, which covers both an origin far
+// outside the boxes and the rounding of (plane - o) idir; intervals are compared with a relative slack of 2^-20 and
+// NaNs (inf - inf for axis-parallel rays) drop out of fminf / fmaxf, which can only widen the interval.
+#define PG_EMBOX_MAX 8
+#if defined(__HIPCC__)
+#define PG_HD __host__ __device__
+#else
+#define PG_HD
+#endif
+// boxes: (lo.xyz, hi.xyz) each, padded; absmax: the largest |coordinate| of any of them.  True: the ray o + t d,
+// t >= tmin, misses every box.
+PG_HD inline bool pg_ray_misses_boxes(const float (*boxes)[6], uint32_t n, float absmax, const float o[3], const float d[3],
+                                      float tmin) {
+    const float eps = 1e-30f;  // slabRay's guard of a zero direction component
+    const float s = 1.52587891e-5f * (fmaxf(fmaxf(fabsf(o[0]), fabsf(o[1])), fabsf(o[2])) + absmax);  // 2^-16
+    float idir[3], pad[3];
+    for (int a = 0; a < 3; ++a) {
+        idir[a] = 1.0f / (fabsf(d[a]) > eps ? d[a] : copysignf(eps, d[a]));
+        pad[a] = s * fabsf(idir[a]);
+    }
+    for (uint32_t b = 0; b < n; ++b) {
+        float tn = tmin, tf = __builtin_huge_valf();
+        for (int a = 0; a < 3; ++a) {
+            const float t0 = (boxes[b][a] - o[a]) * idir[a], t1 = (boxes[b][3 + a] - o[a]) * idir[a];
+            tn = fmaxf(tn, fminf(t0, t1) - pad[a]);
+            tf = fminf(tf, fmaxf(t0, t1) + pad[a]);
+        }
+        if (tn <= tf + 9.53674316e-7f * fabsf(tf)) return false;
+    }
+    return true;
+}
+// Host: the padded boxes of a scene's emitter triangles.  tri_emitter[t]: emitter index + 1 of triangle t, 0 for
+// none.  Returns the number of boxes (0: no emitter triangle) and their largest |coordinate| in *absmax.
+inline uint32_t pg_emitter_boxes(const float *positions, const uint32_t *indices, const uint32_t *tri_emitter, uint32_t nt,
+                                 uint32_t num_emitters, float (*boxes)[6], float *absmax) {
+    const float inf = __builtin_huge_valf();
+    uint32_t n = 0;
+    // one box per emitter while they fit; from the first emitter past PG_EMBOX_MAX on, one union of all
+    const bool single = num_emitters > PG_EMBOX_MAX;
+    for (uint32_t e = 0; e < (single ? 1u : num_emitters); ++e) {
+        float lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf};
+        for (uint32_t t = 0; t < nt; ++t) {
+            if (tri_emitter[t] == 0 || (!single && tri_emitter[t] != e + 1)) continue;
+            for (int k = 0; k < 3; ++k)
+                for (int a = 0; a < 3; ++a) {
+                    const float x = positions[3 * (size_t)indices[3 * (size_t)t + k] + a];
+                    lo[a] = fminf(lo[a], x);
+                    hi[a] = fmaxf(hi[a], x);
+                }
+        }
+        if (!(lo[0] <= hi[0])) continue;  // an emitter without triangles
+        float ext = 0.0f, mag = 0.0f;
+        for (int a = 0; a < 3; ++a) {
+            ext = fmaxf(ext, hi[a] - lo[a]);
+            mag = fmaxf(mag, fmaxf(fabsf(lo[a]), fabsf(hi[a])));
+        }
+        const float padding = 1e-3f * ext + 1e-3f * mag;
+        for (int a = 0; a < 3; ++a) {
+            boxes[n][a] = lo[a] - padding;
+            boxes[n][3 + a] = hi[a] + padding;
+        }
+        ++n;
+    }
+    *absmax = 0.0f;
+    for (uint32_t b = 0; b < n; ++b)
+        for (int a = 0; a < 6; ++a) *absmax = fmaxf(*absmax, fabsf(boxes[b][a]));
+    return n;
+}
 
 // Kernel-side constants of one render context.
 struct GParams {
@@ -281,4 +365,5 @@ struct GParams {
     int32_t exact_mis;       // pg_config.volpath_exact_mis
     int32_t glossy_prior;    // pg_config.glossy_prior
     int32_t path_cull;       // 1: shadeOne decides PF_DOOMED one bounce early and the tracer culls (PG_NO_PATH_CULL: 0)
+    int32_t doom_probe;      // 1: a doomed ray that misses every emitter box is probed, not traced (PG_NO_DOOM_PROBE: 0)
 };

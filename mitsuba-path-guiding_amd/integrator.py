@@ -243,6 +243,8 @@ class Device:
         n = C.c_uint64()
         self._chk(self.lib.pg_get_culled(self.h, C.byref(n)))
         out["culled"] = n.value  # segments whose doomed vertex the tracer culled (pg_capi.h pg_get_culled)
+        self._chk(self.lib.pg_get_probes(self.h, C.byref(n)))
+        out["probes"] = n.value  # segments answered by an any-hit probe (pg_capi.h pg_get_probes)
         return out
 
     def local_pixel_count(self):
