@@ -138,7 +138,7 @@ struct Lane {
     uint32_t P = 0;
     int vtx_slots = 0;
     uint32_t vtxP = 0;  // slot stride of vtx (recording passes only allocate it)
-    DevBuf ray_o, ray_d, hit, thr, rad, prev, pinfo, sh_d, sh_c, vtx, q0, q1, qs, qp, class_q, counters, stack_ovf;
+    DevBuf ray_o, ray_d, hit, thr, rad, pinfo, sh_d, sh_c, vtx, q0, q1, qs, qp, class_q, counters, stack_ovf;
     DevBuf qkey, qsorted, rsort_hist;  // ray-sorted trace queues (PG_RAY_SORT): keys, sorted entries, histograms
     bool sorted = false;               // the queue of the next trace launch is qsorted
     DevBuf tail_stats;                 // k_tail counters of the running chunk (kTailStats u64), copied to h_tail
@@ -431,7 +431,7 @@ SDDev sdView(const Ctx *c) {
 }
 PathDev pathView(const Lane *c) {
     return PathDev{c->ray_o.as<float4>(), c->ray_d.as<float4>(), c->hit.as<float4>(), c->thr.as<float4>(),
-                   c->rad.as<float4>(),   c->prev.as<float4>(),  c->pinfo.as<uint4>(),
+                   c->rad.as<float4>(),   c->pinfo.as<uint4>(),
                    c->sh_d.as<float4>(),  c->sh_c.as<float4>(),  c->vtx.as<float4>(), c->stack_ovf.as<uint32_t>(),
                    c->P,                  c->vtxP,               c->aov.as<float4>()};
 }
@@ -528,7 +528,7 @@ int vertexSlots(const Ctx *c, bool rec) { return rec ? std::max(0, std::min(c->c
 void releasePaths(Ctx *c) {
     for (int li = 0; li < c->nlanes; ++li) {
         Lane &l = c->lanes[li];
-        for (DevBuf *b : {&l.ray_o, &l.ray_d, &l.hit, &l.thr, &l.rad, &l.prev, &l.pinfo, &l.sh_d, &l.sh_c,
+        for (DevBuf *b : {&l.ray_o, &l.ray_d, &l.hit, &l.thr, &l.rad, &l.pinfo, &l.sh_d, &l.sh_c,
                           &l.vtx, &l.q0, &l.q1, &l.qs, &l.qp, &l.class_q, &l.aov, &l.qkey, &l.qsorted})
             b->release();
         l.P = 0;
@@ -572,7 +572,6 @@ pg_status ensurePaths(Ctx *c, uint32_t want, bool rec) {
         HIPC(c, l.hit.alloc(f4));
         HIPC(c, l.thr.alloc(f4));
         HIPC(c, l.rad.alloc(f4));
-        HIPC(c, l.prev.alloc(f4));
         HIPC(c, l.pinfo.alloc(f4));
         HIPC(c, l.sh_d.alloc(f4));
         HIPC(c, l.sh_c.alloc(f4));
@@ -1729,7 +1728,7 @@ static pg_status renderPass(Ctx *c, uint32_t spp, uint32_t sample_offset, int32_
     // (2^26) 646-650, 12 655-660, 9 (2^27) 637-648 Mpaths/s (profiles/r06_chunk/, r06_chunk2/).  So a pass of at
     // least 3 x lanes x 2^26 paths is cut into four rounds of lanes (whole sample layers, at most 2^27 paths a
     // chunk); smaller passes (training, an N-GPU shard) keep 2^25 so every lane still gets several chunks.
-    // A non-recording lane holds ~6.6 GB per 2^25 paths; recording lanes add 32 training vertices per path.
+    // A non-recording lane holds ~6.1 GB per 2^25 paths; recording lanes add 32 training vertices per path.
     const uint64_t total = (uint64_t)npix * spp;
     uint32_t cap = c->cfg.max_paths_in_flight ? c->cfg.max_paths_in_flight : (1u << 25);
     if (!c->cfg.max_paths_in_flight && total >= 3ull * (uint64_t)c->nlanes * (1ull << 26)) {
@@ -1744,12 +1743,12 @@ static pg_status renderPass(Ctx *c, uint32_t spp, uint32_t sample_offset, int32_
             size_t held = 0;
             for (int li = 0; li < c->nlanes; ++li) {
                 const Lane &l = c->lanes[li];
-                for (const DevBuf *b : {&l.ray_o, &l.ray_d, &l.hit, &l.thr, &l.rad, &l.prev, &l.pinfo,
+                for (const DevBuf *b : {&l.ray_o, &l.ray_d, &l.hit, &l.thr, &l.rad, &l.pinfo,
                                         &l.sh_d, &l.sh_c, &l.vtx, &l.q0, &l.q1, &l.qs, &l.qp, &l.class_q, &l.aov})
                     held += b->bytes;
             }
             const int vs = vertexSlots(c, rec);
-            const double perPath = 9.0 * 16 + (4 + PG_NUM_CLASSES) * 4.0 + vs * 16.0 * PG_VTX_F4 + (c->cfg.aovs ? 16.0 : 0.0);
+            const double perPath = 8.0 * 16 + (4 + PG_NUM_CLASSES) * 4.0 + vs * 16.0 * PG_VTX_F4 + (c->cfg.aovs ? 16.0 : 0.0);
             const double fit = 0.7 * (double)(freeB + held) / (perPath * c->nlanes);
             if (fit < (double)cap) cap = std::max<uint32_t>(1u << 20, (uint32_t)fit & ~4095u);
         }

@@ -28,7 +28,7 @@ struct SceneDev {
 // (T before the vertex, p_guide(wo) or -1 when the vertex was not guided)
 #define PG_VTX_F4 4
 struct PathDev {
-    float4 *ray_o, *ray_d, *hit, *thr, *rad, *prev;
+    float4 *ray_o, *ray_d, *hit, *thr, *rad;  // row meanings: pg_layout.h "Path state"
     uint4 *pinfo;
     float4 *sh_d, *sh_c;  // shadow ray (direction, tmax) and contribution; its origin is ray_o
     float4 *vtx;       // [max_vertices][P][PG_VTX_F4]

@@ -58,8 +58,9 @@ __global__ __launch_bounds__(256) void k_camera(GParams g, PathDev p, const uint
     f3 wd = left * d.x + up * d.y + dir * d.z;
     stS(&p.ray_o[slot], make_float4(g.cam_o[0], g.cam_o[1], g.cam_o[2], g.near_clip * invZ));
     stS(&p.ray_d[slot], f4(wd, g.far_clip * invZ));
-    // throughput (1, eta 1) and the previous vertex are implied by depth 1: the first bounce's readers
-    // (shadeOne, envEscapeRadiance) do not load them.  L = 0 is stored: a camera ray that escapes is
+    // throughput (1, eta 1) is implied by depth 1: the first bounce's readers (shadeOne, envEscapeRadiance) do not
+    // load it.  ray_d.w is the far clip along the ray; a bounce ray keeps woPdf there (pg_layout.h "Path state").
+    // L = 0 is stored: a camera ray that escapes is
     // never shaded and k_film reads its L.
     stS(&p.rad[slot], make_float4(0.f, 0.f, 0.f, 0.f));
     stS(&p.pinfo[slot], make_uint4(pix, sample, 1u | (PF_EMITTED_QUERY << 16), 0u));
@@ -97,10 +98,11 @@ __device__ __forceinline__ f3 bsdfAlbedo(const GMat &M) {
 // hit record (t, u, v of a miss; the escape ends the path), and k_film / k_commit add it to L
 // (envHitRadiance): the sum (L + NEE of the last vertex) + environment keeps its order while the
 // last vertex's shadow ray may run in the same launch (k_rays)
+// word: the escaped ray's depth | flags << 16 (pinfo.z; kCameraWord for a camera ray), woPdf: a bounce ray's ray_d.w
+constexpr uint32_t kCameraWord = 1u | (PF_EMITTED_QUERY << 16);  // what k_camera writes to pinfo.z
 __device__ __forceinline__ f3 envEscapeRadiance(const GParams &g, const SceneDev &sc, const PathDev &p, uint32_t slot,
-                                                f3 rd) {
-    const uint4 pi = p.pinfo[slot];
-    const uint32_t depth = pi.z & 0xFFFFu, flags = pi.z >> 16;
+                                                f3 rd, uint32_t word, float woPdf) {
+    const uint32_t depth = word & 0xFFFFu, flags = word >> 16;
     f3 add;
     if (depth == 1) {  // camera ray (throughput 1): the loop-top miss with EEmittedRadiance
         if (!(flags & PF_EMITTED_QUERY) || (g.hide_emitters && !(flags & PF_SCATTERED))) return mk1(0.f);
@@ -108,11 +110,10 @@ __device__ __forceinline__ f3 envEscapeRadiance(const GParams &g, const SceneDev
     } else {
         const float4 T4 = p.thr[slot];
         if (g.hide_emitters && !(flags & PF_SCATTERED)) return mk1(0.f);
-        const float4 pv = p.prev[slot];
         float w = 1.0f;
         if (g.use_nee) {
             const float lumPdf = (flags & PF_PREV_DELTA) ? 0.0f : envPdf(*sc.env, rd) * (1.0f / (float)g.num_emitters);
-            w = miWeight(pv.w, lumPdf);
+            w = miWeight(woPdf, lumPdf);
         }
         add = xyz(T4) * envEval(*sc.env, rd) * w;
     }
@@ -129,8 +130,10 @@ __device__ __forceinline__ float4 envHitRadiance(float4 L, float4 hv) {
 }
 
 
-// PF_DOOMED on the ray (pg_layout.h): shadeOne stores a doomed extension ray's tmin negated
+// A bounce ray's rows (pg_layout.h "Path state"): o = (p, +-tmin), d = (wo, woPdf); its tmax is +inf.
+// PF_DOOMED on the ray: shadeOne stores a doomed extension ray's tmin negated
 __device__ __forceinline__ bool rayDoomed(float4 o) { return (__float_as_uint(o.w) >> 31) != 0; }
+static_assert(PG_RAY_EPSILON == kEpsilon, "pg_ray_tmin uses the ray epsilon");
 // class-queue row of a traced ray: the hit triangle's material class, PG_CLASS_ESCAPED for a miss, or
 // PG_CLASS_CULLED for a doomed ray that hit a non-emitter -- its vertex would do nothing, so the path ends
 // here and its hit record becomes a miss without environment radiance (k_film / k_commit add exact zeros)
@@ -173,6 +176,7 @@ __device__ __forceinline__ void classAppend(int cls, uint32_t slot, const ClassQ
 // closest hits of the rows of queue shard bid % PG_QSHARDS that block bid of nblk takes (a
 // grid-stride loop: k_trace, or the trace blocks of k_rays).
 // ENV: the scene has an environment emitter (escaped paths pick up its radiance)
+// CAM: the rows are camera rays (the chunk's first launch), whose tmin / tmax are in the rows; bounce rays otherwise
 // first: the camera rays' bounce with denoiser features on (pg_config.aovs): the hit record of every
 // path also goes to p.aov, which k_film resolves into albedo and normal (nullptr: off)
 // WIDE (PG_CLOSEST_WIDE, A/B): the closest hits walk the shadow rays' 8-wide quantised BVH (octant order,
@@ -182,7 +186,7 @@ __device__ __forceinline__ void classAppend(int cls, uint32_t slot, const ClassQ
 #ifndef PG_CLOSEST_WIDE
 #define PG_CLOSEST_WIDE 0
 #endif
-template <bool ENV, bool LTOP, bool WIDE = false>
+template <bool ENV, bool LTOP, bool CAM, bool WIDE = false>
 __device__ __forceinline__ void traceRows(const GParams &g, const SceneDev &sc, const PathDev &p, const Queue &q,
                                           const ClassQueues &cqs, float4 *first, uint32_t bid, uint32_t nblk,
                                           const TStack &stk, const float4 *top, int ntop) {
@@ -201,7 +205,7 @@ __device__ __forceinline__ void traceRows(const GParams &g, const SceneDev &sc, 
             // under k_rays' 64-VGPR cap
             slot |= rayDoomed(o) ? 0x80000000u : 0u;
             const float tmin = fabsf(o.w);
-            float tmax = d.w;
+            float tmax = CAM ? d.w : __builtin_huge_valf();
             uint32_t tri = 0xFFFFFFFFu;
             float u = 0, v = 0;
             bool h;
@@ -215,7 +219,7 @@ __device__ __forceinline__ void traceRows(const GParams &g, const SceneDev &sc, 
             float4 hr = make_float4(h ? tmax : 0.0f, __uint_as_float(h ? tri : 0xFFFFFFFFu), u, v);
             if (first) first[slot] = hr;
             if (ENV && !h) {
-                const f3 e = envEscapeRadiance(g, sc, p, slot, xyz(d));
+                const f3 e = envEscapeRadiance(g, sc, p, slot, xyz(d), CAM ? kCameraWord : p.pinfo[slot].z, d.w);
                 hr = make_float4(e.x, hr.y, e.y, e.z);
             }
             cls = hitClass(sc, h, tri, doomed, hr);
@@ -258,6 +262,7 @@ __device__ __forceinline__ void traceRowsPersist(const GParams &g, const SceneDe
     const int lane = threadIdx.x & 63;
     bool active = false, doomed = false;
     uint32_t slot = 0;
+    float woPdf = 0.0f;
     Walk4 w;
     for (;;) {
         const unsigned long long act = __ballot(active);
@@ -268,7 +273,8 @@ __device__ __forceinline__ void traceRowsPersist(const GParams &g, const SceneDe
                 slot = items[cur + rank];
                 const float4 o = ldS(&p.ray_o[slot]), d = ldS(&p.ray_d[slot]);
                 doomed = rayDoomed(o);
-                walk4Start(w, xyz(o), xyz(d), fabsf(o.w), d.w);
+                woPdf = d.w;
+                walk4Start(w, xyz(o), xyz(d), fabsf(o.w), __builtin_huge_valf());
                 active = true;
             }
             cur += min(idle, end - cur);
@@ -282,7 +288,7 @@ __device__ __forceinline__ void traceRowsPersist(const GParams &g, const SceneDe
             float4 hr = make_float4(h ? w.tmax : 0.0f, __uint_as_float(h ? w.hitTri : 0xFFFFFFFFu), w.hu, w.hv);
             if (first) first[slot] = hr;
             if (ENV && !h) {
-                const f3 e = envEscapeRadiance(g, sc, p, slot, w.d);
+                const f3 e = envEscapeRadiance(g, sc, p, slot, w.d, p.pinfo[slot].z, woPdf);
                 hr = make_float4(e.x, hr.y, e.y, e.z);
             }
             cls = hitClass(sc, h, w.hitTri, doomed, hr);
@@ -303,12 +309,12 @@ __device__ __forceinline__ void traceRowsPersist(const GParams &g, const SceneDe
 constexpr uint32_t kPairRing = PG_QSTACK_DEPTH - LDS_STACK;
 template <bool ENV>
 __device__ __forceinline__ void finishWalk(const GParams &g, const SceneDev &sc, const PathDev &p, const Walk4 &w,
-                                           uint32_t slot, bool doomed, float4 *first, int &cls) {
+                                           uint32_t slot, bool doomed, float woPdf, float4 *first, int &cls) {
     const bool h = w.hitTri != 0xFFFFFFFFu;
     float4 hr = make_float4(h ? w.tmax : 0.0f, __uint_as_float(h ? w.hitTri : 0xFFFFFFFFu), w.hu, w.hv);
     if (first) first[slot] = hr;
     if (ENV && !h) {
-        const f3 e = envEscapeRadiance(g, sc, p, slot, w.d);
+        const f3 e = envEscapeRadiance(g, sc, p, slot, w.d, p.pinfo[slot].z, woPdf);
         hr = make_float4(e.x, hr.y, e.y, e.z);
     }
     cls = hitClass(sc, h, w.hitTri, doomed, hr);
@@ -325,6 +331,7 @@ __device__ __forceinline__ void traceRowsPair(const GParams &g, const SceneDev &
         const uint32_t ia = base + threadIdx.x, ib = ia + TRACE_BLOCK;
         uint32_t slotA = 0, slotB = 0;
         bool doomedA = false, doomedB = false;
+        float woPdfA = 0.0f, woPdfB = 0.0f;
         Walk4 a, b;
         walk4Idle(a);
         walk4Idle(b);
@@ -332,24 +339,26 @@ __device__ __forceinline__ void traceRowsPair(const GParams &g, const SceneDev &
             slotA = items[ia];
             const float4 o = ldS(&p.ray_o[slotA]), d = ldS(&p.ray_d[slotA]);
             doomedA = rayDoomed(o);
-            walk4Start(a, xyz(o), xyz(d), fabsf(o.w), d.w);
+            woPdfA = d.w;
+            walk4Start(a, xyz(o), xyz(d), fabsf(o.w), __builtin_huge_valf());
         }
         if (ib < n) {
             slotB = items[ib];
             const float4 o = ldS(&p.ray_o[slotB]), d = ldS(&p.ray_d[slotB]);
             doomedB = rayDoomed(o);
-            walk4Start(b, xyz(o), xyz(d), fabsf(o.w), d.w);
+            woPdfB = d.w;
+            walk4Start(b, xyz(o), xyz(d), fabsf(o.w), __builtin_huge_valf());
         }
         walk4Pair(a, b, sc.nodes, sc.tris, sa, sb);
         int ca = -1, cb = -1;
-        if (ia < n) finishWalk<ENV>(g, sc, p, a, slotA, doomedA, first, ca);
-        if (ib < n) finishWalk<ENV>(g, sc, p, b, slotB, doomedB, first, cb);
+        if (ia < n) finishWalk<ENV>(g, sc, p, a, slotA, doomedA, woPdfA, first, ca);
+        if (ib < n) finishWalk<ENV>(g, sc, p, b, slotB, doomedB, woPdfB, first, cb);
         classAppend(ca, slotA, cqs, s);
         classAppend(cb, slotB, cqs, s);
     }
 }
 
-template <bool ENV>
+template <bool ENV, bool CAM>
 __global__ __launch_bounds__(TRACE_BLOCK) void k_trace(GParams g, SceneDev sc, PathDev p, Queue q, ClassQueues cqs,
                                                        float4 *first) {
     __shared__ uint32_t stack[LDS_STACK * TRACE_BLOCK];
@@ -360,7 +369,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) void k_trace(GParams g, SceneDev sc, P
         for (uint32_t k = threadIdx.x; k < (uint32_t)ntop * PG_TOP_NODE_F4; k += TRACE_BLOCK) top[k] = sc.nodes[k];
         __syncthreads();
     }
-    traceRows<ENV, PG_TRACE_LDS_TOP != 0>(g, sc, p, q, cqs, first, blockIdx.x, gridDim.x, threadStack(stack, p.stack_ovf),
+    traceRows<ENV, PG_TRACE_LDS_TOP != 0, CAM>(g, sc, p, q, cqs, first, blockIdx.x, gridDim.x, threadStack(stack, p.stack_ovf),
                                           top, ntop);
 }
 
@@ -482,14 +491,14 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PG_
         else if (PG_TRACE_PERSIST && !PG_RAYS_LDS_TOP && !PG_CLOSEST_WIDE && PG_BVH4 && PG_QNODE_QUANT)
             traceRowsPersist<ENV>(g, sc, p, q, cqs, nullptr, blockIdx.x, trace_blocks, sa);
         else
-            traceRows<ENV, PG_RAYS_LDS_TOP != 0, PG_CLOSEST_WIDE != 0>(g, sc, p, q, cqs, nullptr, blockIdx.x, trace_blocks,
+            traceRows<ENV, PG_RAYS_LDS_TOP != 0, false, PG_CLOSEST_WIDE != 0>(g, sc, p, q, cqs, nullptr, blockIdx.x, trace_blocks,
                                                  sa, top, ntop);
     }
 #else
     if (blockIdx.x < shadow_blocks)
         shadowRows(sc, p, shq, blockIdx.x, shadow_blocks, threadWideStack(stack, p.stack_ovf));
     else
-        traceRows<ENV, false>(g, sc, p, q, cqs, nullptr, blockIdx.x - shadow_blocks,
+        traceRows<ENV, false, false>(g, sc, p, q, cqs, nullptr, blockIdx.x - shadow_blocks,
                               gridDim.x - probe_blocks - shadow_blocks, threadStack(stack, p.stack_ovf), nullptr, 0);
 #endif
 }
@@ -526,6 +535,7 @@ __device__ __forceinline__ uint32_t rayOrderKey(const SDDev &sd, f3 o, f3 d) {
 // one bounce of Li for the path in `slot` (progressive_path.cpp:149-306 + guiding): reads its state,
 // writes the next one; alive = an extension ray was written, shadow = a shadow ray was written (sh_*)
 // mats: the material table (global memory, or a block's LDS copy); wantKey: compute rkey (PG_RAY_SORT)
+
 // the per-bounce half of a path's info record (depth | flags, vertex count): pixel and sample never
 // change after k_camera, so an 8-B store replaces the 16-B rewrite
 __device__ __forceinline__ void stPinfoZW(uint4 *p, uint32_t z, uint32_t w) {
@@ -588,23 +598,31 @@ __device__ __forceinline__ void shadeOne(const GParams &g, const SceneDev &sc, c
     bool watched = false;
 #endif
     do {
-        uint4 pi = ldS(&p.pinfo[slot]);
+        const uint4 pi = ldS(&p.pinfo[slot]);
         const uint32_t pix = pi.x, sample = pi.y;
 #if PG_WATCH
         watched = pix == pgWatch[0] && sample == pgWatch[1];
 #endif
-        uint32_t depth = pi.z & 0xFFFFu, flags = pi.z >> 16, nv = pi.w;
+        const float4 rd4 = ldS(&p.ray_d[slot]);
         float4 hv = ldS(&p.hit[slot]);
-        // a camera ray's state is implied (k_camera stores neither throughput nor prev)
+        uint32_t depth = pi.z & 0xFFFFu, flags = pi.z >> 16, nv = pi.w;
+        // a camera ray's state is implied (k_camera stores no throughput)
         float4 T4 = depth == 1 ? make_float4(1.f, 1.f, 1.f, 1.f) : ldS(&p.thr[slot]);
-        float4 L4 = depth == 1 ? make_float4(0.f, 0.f, 0.f, 0.f) : ldS(&p.rad[slot]);
         f3 T = xyz(T4);
-        L = xyz(L4);
+        // L is loaded where the vertex first needs it: before it adds emission or snapshots a training vertex.  Most
+        // vertices of a non-recording pass do neither, and the dirtyL store below is the only one either way.
+        bool haveL = depth == 1;
+        auto loadL = [&]() {
+            if (!haveL) {
+                L = xyz(ldS(&p.rad[slot]));
+                haveL = true;
+            }
+        };
+        if (PG_WATCH) loadL();
         float eta = T4.w;
         uint32_t tri = __float_as_uint(hv.y);
         if (tri == 0xFFFFFFFFu) break;  // escaped: no environment emitter
         const uint32_t key = rngKey(pix, g.seed);
-        const float4 rd4 = ldS(&p.ray_d[slot]);
         f3 rd = xyz(rd4);
 #if PG_SD_PREFETCH
         // the guided lookup's jump-grid cell and leaf record, fetched from the ray's o + t d while the triangle and
@@ -635,16 +653,17 @@ __device__ __forceinline__ void shadeOne(const GParams &g, const SceneDev &sc, c
         // ---- finish the previous bounce: emitter hit by the sampled direction (MIS), then RR
         if (depth > 1) {
             if (h.emitter >= 0) {
-                float4 pv = ldS(&p.prev[slot]);
+                // the pdf the previous vertex sampled this direction with, and the side it left that vertex on
+                const float prevPdf = rd4.w;  // a bounce ray's row (pg_layout.h "Path state")
                 float lumPdf = 0.0f;
                 if (g.use_nee && !(flags & PF_PREV_DELTA)) {
-                    f3 prevRefN = xyz(pv);
-                    if (dot(rd, prevRefN) >= 0 && dot(rd, h.shN) < 0) {
+                    if ((flags & PF_PREV_FRONT) && dot(rd, h.shN) < 0) {
                         const GEmitter &em = sc.ems[h.emitter];
                         lumPdf = em.inv_area * (hv.x * hv.x) / absDot(rd, h.shN) * (1.0f / (float)g.num_emitters);
                     }
                 }
-                float w = g.use_nee ? miWeight(pv.w, lumPdf) : 1.0f;
+                float w = g.use_nee ? miWeight(prevPdf, lumPdf) : 1.0f;
+                loadL();
                 L = L + T * Le * w;
                 dirtyL = true;
             }
@@ -683,6 +702,7 @@ __device__ __forceinline__ void shadeOne(const GParams &g, const SceneDev &sc, c
         const GMat M = mats[h.mat];
 #endif
         if ((flags & PF_EMITTED_QUERY) && h.emitter >= 0 && (!g.hide_emitters || (flags & PF_SCATTERED))) {
+            loadL();
             L = L + T * Le;
             dirtyL = true;
         }
@@ -817,6 +837,7 @@ __device__ __forceinline__ void shadeOne(const GParams &g, const SceneDev &sc, c
                 if (g.record && !(bs.type & EDelta) && nv < (uint32_t)g.max_vertices) {
                     float cu, cv;
                     dirToCanonical(wo, cu, cv);
+                    loadL();
                     float4 *vb = p.vtx + ((size_t)nv * p.vtxP + slot) * PG_VTX_F4;
                     stS(vb + 0, f4(h.p, woPdf));
                     stS(vb + 1, f4(Tn, __uint_as_float(packCanonical(cu, cv))));
@@ -826,7 +847,7 @@ __device__ __forceinline__ void shadeOne(const GParams &g, const SceneDev &sc, c
                     vtxIndex = nv;
                     nv++;
                 }
-                float tmin = kEpsilon * fmaxf(fmaxf(fmaxf(fabsf(h.p.x), fabsf(h.p.y)), fabsf(h.p.z)), kEpsilon);
+                const float tmin = pg_ray_tmin(h.p.x, h.p.y, h.p.z);
                 const float etaN = eta * bs.eta;
                 // the next vertex's exits, decided here (PF_DOOMED): its depth tests, and its roulette draw against
                 // the throughput and eta it will load from thr[slot]
@@ -842,15 +863,16 @@ __device__ __forceinline__ void shadeOne(const GParams &g, const SceneDev &sc, c
                     const float po[3] = {h.p.x, h.p.y, h.p.z}, pd[3] = {wo.x, wo.y, wo.z};
                     probe = pg_ray_misses_boxes(sc.em_box, sc.num_em_boxes, sc.em_absmax, po, pd, tmin);
                 }
+                // the bounce ray's rows (pg_layout.h "Path state")
                 stS(&p.ray_o[slot], f4(h.p, doomed ? -tmin : tmin));
-                stS(&p.ray_d[slot], f4(wo, __int_as_float(0x7f800000)));
+                stS(&p.ray_d[slot], f4(wo, woPdf));
                 if (probe) {  // the path ends here: the hit record a culled hit gets, no state for a next vertex
                     stS(&p.hit[slot], make_float4(0.0f, __uint_as_float(0xFFFFFFFFu), 0.0f, 0.0f));
                 } else {
                     stS(&p.thr[slot], f4(Tn, etaN));
-                    stS(&p.prev[slot], f4(refN, woPdf));
-                    flags = (flags & ~(PF_EMITTED_QUERY | PF_PREV_DELTA)) | ((bs.type & EDelta) ? PF_PREV_DELTA : 0u) |
-                            (doomed ? PF_DOOMED : 0u);
+                    flags = (flags & ~(PF_EMITTED_QUERY | PF_PREV_DELTA | PF_PREV_FRONT)) |
+                        ((bs.type & EDelta) ? PF_PREV_DELTA : 0u) | (doomed ? PF_DOOMED : 0u) |
+                        (pg_prev_front(wo.x, wo.y, wo.z, refN.x, refN.y, refN.z) ? PF_PREV_FRONT : 0u);
                     stPinfoZW(&p.pinfo[slot], (depth + 1) | (flags << 16), nv);
                     alive = true;
                     if (wantKey) rkey = rayOrderKey(sd, h.p, wo);
@@ -1090,12 +1112,12 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PG_
             if (!alive) break;
             // traceRows for this path
             const float4 o = ldS(&p.ray_o[slot]), d = ldS(&p.ray_d[slot]);
-            float tmax = d.w, u = 0, v = 0;
+            float tmax = __builtin_huge_valf(), u = 0, v = 0;
             tri = 0xFFFFFFFFu;
             const bool h = traverse<false>(sc.nodes, sc.tris, xyz(o), xyz(d), fabsf(o.w), tmax, tri, u, v, stk);
             float4 hr = make_float4(h ? tmax : 0.0f, __uint_as_float(h ? tri : 0xFFFFFFFFu), u, v);
             if (ENV && !h) {
-                const f3 e = envEscapeRadiance(g, sc, p, slot, xyz(d));
+                const f3 e = envEscapeRadiance(g, sc, p, slot, xyz(d), p.pinfo[slot].z, d.w);
                 hr = make_float4(e.x, hr.y, e.y, e.z);
             }
             const int cls = hitClass(sc, h, tri, rayDoomed(o), hr);
@@ -1570,8 +1592,14 @@ void pg_launch_trace(hipStream_t s, const GParams &g, const SceneDev &sc, const 
     for (int c = 0; c < PG_CLASS_ROWS; ++c) cq.q[c] = class_queues[c];
     const dim3 grid = shardGrid(max_shard, TRACE_BLOCK, TRACE_MAX_BLOCKS / PG_QSHARDS);
     float4 *first = first_bounce ? p.aov : nullptr;
-    if (sc.env) hipLaunchKernelGGL(k_trace<true>, grid, dim3(TRACE_BLOCK), 0, s, g, sc, p, q, cq, first);
-    else hipLaunchKernelGGL(k_trace<false>, grid, dim3(TRACE_BLOCK), 0, s, g, sc, p, q, cq, first);
+    // the chunk's first launch traces k_camera's rows, every later one shadeOne's (pg_layout.h "Path state")
+    if (first_bounce) {
+        if (sc.env) hipLaunchKernelGGL((k_trace<true, true>), grid, dim3(TRACE_BLOCK), 0, s, g, sc, p, q, cq, first);
+        else hipLaunchKernelGGL((k_trace<false, true>), grid, dim3(TRACE_BLOCK), 0, s, g, sc, p, q, cq, first);
+    } else {
+        if (sc.env) hipLaunchKernelGGL((k_trace<true, false>), grid, dim3(TRACE_BLOCK), 0, s, g, sc, p, q, cq, first);
+        else hipLaunchKernelGGL((k_trace<false, false>), grid, dim3(TRACE_BLOCK), 0, s, g, sc, p, q, cq, first);
+    }
 }
 template <bool ENV>
 static void launchShade(hipStream_t s, int cls, dim3 grid, const GParams &g, const SceneDev &sc, const SDDev &sd,

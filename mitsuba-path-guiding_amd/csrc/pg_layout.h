@@ -254,10 +254,30 @@ inline void pg_qnode_box(const float *node, int s, float lo[3], float hi[3]) {
 #define PG_TCLASS_EMITTER 0x80u
 #define PG_TCLASS_MASK 0x7Fu
 
+// Path state of the surface wavefront, one 16-B row per slot and array (PathDev, pg_kernels.h):
+//   camera ray (k_camera):  ray_o = (camera position, near clip along the ray)   ray_d = (direction, far clip)
+//                           pinfo = (pixel, sample, 1 | PF_EMITTED_QUERY << 16, 0)   rad = 0   thr: implied (1, eta 1)
+//   bounce ray (shadeOne):  ray_o = (p, +-tmin)   ray_d = (wo, woPdf)   thr = (T, eta)
+//                           pinfo.zw = (depth | flags << 16, training-vertex count), an 8-B store
+// A bounce ray's tmax is +inf, so the tracers take it as a constant (their CAM template flag tells camera rows from
+// bounce rows) and ray_d.w carries woPdf, the solid-angle pdf wo was sampled with.  It is read only by a vertex that
+// lands on an emitter and by an escape into the environment emitter, for the MIS weight against next-event
+// estimation; both hold ray_d already.  tmin = pg_ray_tmin(p) stays in ray_o.w with PF_DOOMED in its sign: recomputing
+// it in the tracers and moving depth | flags into ray_d.w (so that pinfo is not rewritten) was built and measured,
+// and cost k_rays<false> seven more spilled VGPRs and 15 % of its time (DESIGN.md section 5 "Lean state").
+// There is no row for the previous vertex: PF_PREV_FRONT below replaces its reference normal.  L (rad) is loaded
+// only by a vertex that adds emission or snapshots a training vertex.
+// A path that ends while it still owes a shadow ray keeps ray_o = (p, 0): the shadow rows derive their own tmin.
+//
 // Path-state flags (pinfo.z high bits; stPinfoZW writes depth | flags << 16 with the vertex count)
 #define PF_SCATTERED 0x1u
 #define PF_EMITTED_QUERY 0x2u
 #define PF_PREV_DELTA 0x4u
+// The extension ray leaves the vertex that wrote it on the side of that vertex's reference normal:
+// pg_prev_front(wo, refN), with refN = 0 (transmissive or back-side lobes: always true) as the emitter-hit MIS of
+// the next vertex wants it.  That vertex's ray direction is this vertex's wo bit for bit, so the writer evaluates
+// the test and the reader needs neither the normal nor a row to keep it in.
+#define PF_PREV_FRONT 0x10u
 // The vertex this ray leads to ends before it samples anything: the shader that wrote the ray already made its
 // Russian-roulette draw (same key, sample, dimension, throughput and eta the vertex would use) and lost, or the
 // vertex is past depth_cap / at max_depth.  Such a vertex can only add the emission of an emitter it hits, so
@@ -291,6 +311,20 @@ inline void pg_qnode_box(const float *node, int s, float lo[3], float hi[3]) {
 #else
 #define PG_HD
 #endif
+// tmin of a ray that leaves a surface at p (Epsilon * max(max |p_i|, Epsilon), the reference's ray epsilon; Epsilon
+// is pg_device.h kEpsilon).  shadeOne computes it once per extension ray, for its box test and for ray_o.w.
+#define PG_RAY_EPSILON 1e-4f
+PG_HD inline float pg_ray_tmin(float px, float py, float pz) {
+    return PG_RAY_EPSILON * fmaxf(fmaxf(fmaxf(fabsf(px), fabsf(py)), fabsf(pz)), PG_RAY_EPSILON);
+}
+// PF_PREV_FRONT of an extension ray wo written at a vertex with reference normal n: dot(wo, n) >= 0, summed in
+// pg_device.h dot's order and never contracted
+PG_HD inline bool pg_prev_front(float wx, float wy, float wz, float nx, float ny, float nz) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    return wx * nx + wy * ny + wz * nz >= 0;
+}
 // boxes: (lo.xyz, hi.xyz) each, padded; absmax: the largest |coordinate| of any of them.  True: the ray o + t d,
 // t >= tmin, misses every box.
 PG_HD inline bool pg_ray_misses_boxes(const float (*boxes)[6], uint32_t n, float absmax, const float o[3], const float d[3],
