@@ -357,6 +357,37 @@ pg_status pg_reset_film(void *ctx);
  * space, 0).  A camera ray that escapes contributes Denoiser::Sample's defaults: albedo 0, normal
  * (0, 0, -1).  Cleared by pg_reset_film.  Either pointer may be NULL. */
 pg_status pg_read_aovs(void *ctx, float *albedo, float *normal);
+/* ---- filtered film: the reference's reconstruction filter (ImageBlock::put, imageblock.h:151-196) ----------
+ * New entry points; pg_config, pg_stats and PG_ABI_VERSION are unchanged.  While no filter is set, nothing
+ * below is allocated or launched and every other result is bit for bit what it was.
+ *
+ * pg_rfilter_table builds the reference's discretised table (ReconstructionFilter::configure,
+ * rfilter.cpp:38-54; src/rfilters/{box,tent,gaussian}.cpp): values[i] = eval(radius * i / 31) for i < 31,
+ * scaled by 1 / (sum * 2 * radius / 31), values[31] = 0.  PG_RFILTER_BOX: radius 0.5; PG_RFILTER_TENT: radius 1;
+ * PG_RFILTER_GAUSSIAN: param = stddev (0 = the default 0.5), radius 4 * stddev.  Needs no device or context. */
+enum { PG_RFILTER_BOX = 0, PG_RFILTER_TENT = 1, PG_RFILTER_GAUSSIAN = 2 };
+pg_status pg_rfilter_table(int32_t type, float param, float *radius_out, float *values_out /* [32] */);
+/* Turn the filtered film on with an arbitrary 32-entry table (negative lobes allowed: Mitsuba's own table of
+ * mitchell, catmullrom or lanczos works), 0 < radius <= 4, else PG_ERR_INVALID; values == NULL turns it off.
+ * After pg_create and before the first render pass (PG_ERR_STATE afterwards); path and volpath integrators;
+ * PG_ERR_INVALID with the banded camera map (PG_CAMERA_BANDS).  The box film, sumsq and the feature buffers
+ * keep accumulating per pixel exactly as without a filter.
+ *
+ * Every sample the box film takes (after the max_component_value clamp; samples ImageBlock::put rejects are
+ * dropped) is splatted with W = width, r = radius, (jx, jy) = the camera's jitter of the sample:
+ *   pos_x = ((float)(pix % W) + jx) - 0.5f                                   (float32, no contraction; y alike)
+ *   columns X = max(ceil(pos_x - r), 0) .. min(floor(pos_x + r), W - 1)      (clipped to the whole image)
+ *   wx[X] = values[min((int)fabsf(((float)X - pos_x) * (31.0f / r)), 31)],   w = wx * wy  (float32)
+ *   acc[Y][X][c] += llrint((double)w * (double)L_c * 2^28), c = r, g, b;     acc[Y][X][3] += llrint((double)w * 2^28)
+ * Signed 64-bit sums in units of 2^-28 (~3.7e-9 per tap): exact, so the film does not depend on chunk sizes,
+ * lanes, launch variants or the shard split.  Range: |sum| < 2^35 per pixel and channel.
+ *
+ * pg_read_film_filtered: raw = width*height*4 int64 (sum w r, sum w g, sum w b, sum w); rgbw = the same as
+ * (float)((double)raw * 2^-28); either may be NULL.  A rank's buffer covers the whole image: its tiles plus the
+ * border its samples reach (ceil(radius - 0.5) pixels).  The developed pixel is rgb / w (hdrfilm).
+ * PG_ERR_STATE when no filter is set.  pg_reset_film clears it; pg_comm_reduce_film sums it (int64, exact). */
+pg_status pg_set_rfilter(void *ctx, float radius, const float *values /* [32] or NULL */);
+pg_status pg_read_film_filtered(void *ctx, float *rgbw, int64_t *raw);
 pg_status pg_get_stats(void *ctx, pg_stats *stats);
 /* Path integrator: segments (counted in pg_stats.segments, not in escaped) whose hit was culled by the
  * closest-hit kernels since create: the ray's next vertex had already lost its Russian roulette, or was past the

@@ -20,6 +20,7 @@ PG_FRACTION_FIXED, PG_FRACTION_ALBEDO, PG_FRACTION_THROUGHPUT, PG_FRACTION_LEARN
 MAJORANT_CELL = 16  # voxels per majorant-grid cell edge (pg_layout.h PG_MAJORANT_CELL / oracle/orc_medium.h)
 PG_DIST_BECKMANN, PG_DIST_GGX = 0, 1
 PG_MAT_TWOSIDED, PG_MAT_NONLINEAR, PG_MAT_SAMPLE_ALL = 1, 2, 4
+PG_RFILTER_BOX, PG_RFILTER_TENT, PG_RFILTER_GAUSSIAN = 0, 1, 2
 
 # EBSDFType bits (include/mitsuba/render/bsdf.h:224-262)
 ENull, EDiffuseReflection, EDiffuseTransmission, EGlossyReflection = 0x1, 0x2, 0x4, 0x8
@@ -172,6 +173,9 @@ SIGNATURES = [
     ("pg_read_film", C.c_int32, [VP, VP, VP]),
     ("pg_reset_film", C.c_int32, [VP]),
     ("pg_read_aovs", C.c_int32, [VP, VP, VP]),
+    ("pg_rfilter_table", C.c_int32, [C.c_int32, C.c_float, C.POINTER(C.c_float), VP]),
+    ("pg_set_rfilter", C.c_int32, [VP, C.c_float, VP]),
+    ("pg_read_film_filtered", C.c_int32, [VP, VP, VP]),
     ("pg_get_stats", C.c_int32, [VP, C.POINTER(pg_stats)]),
     ("pg_get_culled", C.c_int32, [VP, C.POINTER(C.c_uint64)]),
     ("pg_get_probes", C.c_int32, [VP, C.POINTER(C.c_uint64)]),

@@ -233,6 +233,15 @@ struct Ctx {
     // film
     DevBuf film, film_sq;
     DevBuf aov_albedo, aov_normal;  // per-pixel denoiser feature sums (pg_config.aovs)
+    // reconstruction-filtered film (pg_set_rfilter): nothing is allocated or launched while `filtered` is false
+    bool filtered = false;
+    bool filter_direct = false;  // PG_FILM_FILTER_DIRECT=1, or the padded tile exceeds 64 KiB of LDS
+    bool rendered = false;       // a render pass ran: the filter can no longer change
+    float filter_radius = 0;
+    float filter_values[32] = {};
+    DevBuf film_acc, filter_tab, tile_first, tile_origin;
+    std::vector<uint32_t> h_tile_first;  // local tile k = local pixels [h_tile_first[k], h_tile_first[k + 1])
+    std::vector<uint32_t> h_tile_origin; // (x, y) pairs
     // records
     DevBuf records, rec_count;
     uint64_t rec_capacity = 0;
@@ -839,6 +848,127 @@ uint32_t cameraBands() {
     return e && *e ? (uint32_t)std::strtoul(e, nullptr, 10) : 0u;
 }
 
+// ---- reconstruction-filtered film (pg_set_rfilter) ------------------------------------------------------
+// device side of the filter: the table, the local tiles' pixel ranges and origins, and the zeroed sums
+// (needs the scene's film size and tile shard; called by whichever of pg_set_rfilter / pg_upload_scene comes last)
+static pg_status setupFiltered(Ctx *c) {
+    const size_t n = (size_t)c->g.width * c->g.height * 4;
+    HIPC(c, c->film_acc.alloc(n * 8));
+    HIPC(c, hipMemsetAsync(c->film_acc.p, 0, n * 8, c->stream));
+    HIPC(c, c->filter_tab.alloc(sizeof(c->filter_values)));
+    HIPC(c, hipMemcpyAsync(c->filter_tab.p, c->filter_values, sizeof(c->filter_values), hipMemcpyHostToDevice, c->stream));
+    pg_status s;
+    if ((s = upload(c, c->tile_first, c->h_tile_first))) return s;
+    if ((s = upload(c, c->tile_origin, c->h_tile_origin))) return s;
+    HIPC(c, hipStreamSynchronize(c->stream));
+    const char *e = std::getenv("PG_FILM_FILTER_DIRECT");
+    const int border = (int)std::ceil(c->filter_radius - 0.5f);
+    c->filter_direct = (e && std::atoi(e) != 0) || pg_film_filter_lds_bytes(c->cfg.tile_size, border) > 65536;
+    return PG_OK;
+}
+// k_film_filtered for the chunk k_film has just been launched for (same stream, pixel order and path view)
+static void launchFilmFiltered(Ctx *c, hipStream_t s, const GParams &g, const SceneDev &sc, const PathDev &p,
+                               const uint32_t *pixels, uint32_t pb, uint32_t np, uint32_t nl, uint32_t sample_base) {
+    if (!np || !nl) return;
+    FilmFilter f{};
+    f.radius = c->filter_radius;
+    f.scale = 31.0f / c->filter_radius;
+    f.border = (int32_t)std::ceil(c->filter_radius - 0.5f);
+    f.tile = c->cfg.tile_size;
+    f.values = c->filter_tab.as<float>();
+    f.acc = c->film_acc.as<unsigned long long>();
+    f.tile_first = c->tile_first.as<uint32_t>();
+    f.tile_origin = c->tile_origin.as<uint2>();
+    uint32_t tile0 = 0, ntiles = 0;
+    if (!c->filter_direct) {  // the local tiles the chunk's pixel range [pb, pb + np) touches
+        const std::vector<uint32_t> &tf = c->h_tile_first;
+        tile0 = (uint32_t)(std::upper_bound(tf.begin(), tf.end(), pb) - tf.begin()) - 1;
+        ntiles = (uint32_t)(std::upper_bound(tf.begin(), tf.end(), pb + np - 1) - tf.begin()) - tile0;
+    }
+    pg_launch_film_filtered(s, g, sc, p, f, pixels, pb, np, nl, sample_base, tile0, ntiles);
+}
+
+pg_status pg_rfilter_table(int32_t type, float param, float *radius_out, float *values_out) {
+    if (!radius_out || !values_out) return fail(nullptr, PG_ERR_INVALID, "pg_rfilter_table: null argument");
+    float radius, stddev = 0.5f;
+    switch (type) {
+        case PG_RFILTER_BOX: radius = 0.5f; break;
+        case PG_RFILTER_TENT: radius = 1.0f; break;
+        case PG_RFILTER_GAUSSIAN:
+            if (param != 0) stddev = param;
+            if (!(stddev > 0) || !std::isfinite(stddev)) return fail(nullptr, PG_ERR_INVALID, "pg_rfilter_table: bad stddev");
+            radius = 4 * stddev;
+            break;
+        default: return fail(nullptr, PG_ERR_INVALID, "pg_rfilter_table: unknown filter type");
+    }
+    // math::fastexp as pg_fastmath.h states it for the device: the double libm call rounded to float
+    auto fastexp = [](float x) { return (float)std::exp((double)x); };
+    auto eval = [&](float x) -> float {
+        switch (type) {
+            case PG_RFILTER_BOX: return std::fabs(x) <= radius ? 1.0f : 0.0f;                    // box.cpp:46-48
+            case PG_RFILTER_TENT: return std::max(0.0f, 1.0f - std::fabs(x / radius));           // tent.cpp:42-44
+            default: {                                                                            // gaussian.cpp:52-57
+                const float alpha = -1.0f / (2.0f * stddev * stddev);
+                return std::max(0.0f, fastexp(alpha * x * x) - fastexp(alpha * radius * radius));
+            }
+        }
+    };
+    // ReconstructionFilter::configure (rfilter.cpp:38-54)
+    float sum = 0.0f;
+    for (int i = 0; i < 31; ++i) {
+        values_out[i] = eval((radius * i) / 31);
+        sum += values_out[i];
+    }
+    values_out[31] = 0.0f;
+    sum *= 2 * radius / 31;
+    const float normalization = 1.0f / sum;
+    for (int i = 0; i < 31; ++i) values_out[i] *= normalization;
+    *radius_out = radius;
+    return PG_OK;
+}
+
+pg_status pg_set_rfilter(void *ctx, float radius, const float *values) {
+    Ctx *c = (Ctx *)ctx;
+    if (!c) return fail(nullptr, PG_ERR_INVALID, "pg_set_rfilter: null context");
+    if (c->rendered) return fail(c, PG_ERR_STATE, "pg_set_rfilter: a render pass has already run");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    if (!values) {  // off again: as if never set
+        c->filtered = false;
+        for (DevBuf *b : {&c->film_acc, &c->filter_tab, &c->tile_first, &c->tile_origin}) b->release();
+        return PG_OK;
+    }
+    if (!(radius > 0) || !(radius <= 4)) return fail(c, PG_ERR_INVALID, "pg_set_rfilter: need 0 < radius <= 4");
+    for (int i = 0; i < 32; ++i)
+        if (!std::isfinite(values[i])) return fail(c, PG_ERR_INVALID, "pg_set_rfilter: non-finite table entry");
+    if (cameraBands() > 0)
+        return fail(c, PG_ERR_INVALID, "pg_set_rfilter: not supported with the banded camera map (PG_CAMERA_BANDS)");
+    c->filter_radius = radius;
+    std::memcpy(c->filter_values, values, sizeof(c->filter_values));
+    c->filtered = true;
+    return c->has_scene ? setupFiltered(c) : PG_OK;
+}
+
+pg_status pg_read_film_filtered(void *ctx, float *rgbw, int64_t *raw) {
+    Ctx *c = (Ctx *)ctx;
+    if (!c) return fail(nullptr, PG_ERR_INVALID, "pg_read_film_filtered: null context");
+    if (!c->has_scene) return fail(c, PG_ERR_STATE, "pg_read_film_filtered: no scene");
+    if (!c->filtered) return fail(c, PG_ERR_STATE, "pg_read_film_filtered: no filter set (pg_set_rfilter)");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    const size_t n = (size_t)c->g.width * c->g.height * 4;
+    std::vector<int64_t> tmp;
+    int64_t *dst = raw;
+    if (!dst && rgbw) {
+        tmp.resize(n);
+        dst = tmp.data();
+    }
+    if (!dst) return PG_OK;
+    HIPC(c, hipMemcpyAsync(dst, c->film_acc.p, n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    if (rgbw)
+        for (size_t i = 0; i < n; ++i) rgbw[i] = (float)((double)dst[i] * 0x1p-28);
+    return PG_OK;
+}
+
 pg_status pg_upload_scene(void *ctx, const pg_scene_desc *d) {
     Ctx *c = (Ctx *)ctx;
     if (!c || !d) return fail(c, PG_ERR_INVALID, "pg_upload_scene: null argument");
@@ -1100,9 +1230,14 @@ pg_status pg_upload_scene(void *ctx, const pg_scene_desc *d) {
     // tile shard of this rank: 32x32 tiles dealt round-robin
     const uint32_t T = c->cfg.tile_size, tx = (cam.width + T - 1) / T, ty = (cam.height + T - 1) / T;
     c->local_pixels.clear();
+    c->h_tile_first.clear();
+    c->h_tile_origin.clear();
     for (uint32_t t = 0; t < tx * ty; ++t) {
         if ((int32_t)(t % (uint32_t)c->cfg.world_size) != c->cfg.rank) continue;
         uint32_t x0 = (t % tx) * T, y0 = (t / tx) * T;
+        c->h_tile_first.push_back((uint32_t)c->local_pixels.size());
+        c->h_tile_origin.push_back(x0);
+        c->h_tile_origin.push_back(y0);
         const uint32_t x1 = std::min(x0 + T, cam.width), y1 = std::min(y0 + T, cam.height);
         // within a tile, PG_PIXEL_BLOCK^2 pixel blocks (one wave of camera rays per 8x8 block) in
         // row-major block order; 0 = plain row-major.  Per-pixel results do not depend on the order.
@@ -1112,6 +1247,7 @@ pg_status pg_upload_scene(void *ctx, const pg_scene_desc *d) {
                 for (uint32_t y = by; y < std::min(by + B, y1); ++y)
                     for (uint32_t x = bx; x < std::min(bx + B, x1); ++x) c->local_pixels.push_back(y * cam.width + x);
     }
+    c->h_tile_first.push_back((uint32_t)c->local_pixels.size());
     if ((s = upload(c, c->d_local_pixels, c->local_pixels))) return s;
     {  // the surface path's pixel order: bands {r, r + 8, r + 16, ...} of the local pixels as the r-th eighth
         const uint32_t nb = cameraBands(), np = (uint32_t)c->local_pixels.size();
@@ -1138,6 +1274,7 @@ pg_status pg_upload_scene(void *ctx, const pg_scene_desc *d) {
         HIPC(c, hipMemsetAsync(c->aov_albedo.p, 0, fb, c->stream));
         HIPC(c, hipMemsetAsync(c->aov_normal.p, 0, fb, c->stream));
     }
+    if (c->filtered && (s = setupFiltered(c))) return s;
     HIPC(c, c->rec_count.alloc(16));
     HIPC(c, hipMemsetAsync(c->rec_count.p, 0, 16, c->stream));
     c->rec_host_count = 0;
@@ -1399,6 +1536,8 @@ pg_status volWavefrontPass(Ctx *c, const GParams &g, const SceneDev &sc, const V
         }
         pg_launch_film(l.stream, g, sc, lp, c->d_local_pixels.as<uint32_t>(), l.pb, l.np, l.nl, c->film.as<float4>(),
                        c->film_sq.as<float4>());
+        if (c->filtered)
+            launchFilmFiltered(c, l.stream, g, sc, lp, c->d_local_pixels.as<uint32_t>(), l.pb, l.np, l.nl, l.sample_base);
         HIPC(c, hipGetLastError());
         HIPC(c, hipEventRecord(c->film_order, l.stream));
         HIPC(c, hipEventRecord(l.span.b, l.stream));
@@ -1654,6 +1793,8 @@ pg_status renderVolpath(Ctx *c, uint32_t spp, uint32_t sample_offset, bool rec) 
         }
         pg_launch_film(c->stream, g, sc, pv, c->d_local_pixels.as<uint32_t>(), pb, np, nl, c->film.as<float4>(),
                        c->film_sq.as<float4>());
+        if (c->filtered)
+            launchFilmFiltered(c, c->stream, g, sc, pv, c->d_local_pixels.as<uint32_t>(), pb, np, nl, chunks[ci].sample_base);
         HIPC(c, hipGetLastError());
         c->stats.paths += (uint64_t)np * nl;
     }
@@ -1711,6 +1852,7 @@ pg_status pg_render_pass(void *ctx, uint32_t spp, uint32_t sample_offset, int32_
     if (!c->has_scene) return fail(c, PG_ERR_STATE, "pg_render_pass: no scene uploaded");
     if (c->cancel.load()) return fail(c, PG_ERR_CANCELLED, "cancelled");
     HIPC(c, hipSetDevice(c->cfg.device));
+    c->rendered = true;
     const pg_status s = renderPass(c, spp, sample_offset, record);
     if (s) drainLanes(c);
     return s;
@@ -1933,6 +2075,9 @@ static pg_status renderPass(Ctx *c, uint32_t spp, uint32_t sample_offset, int32_
         HIPC(c, hipStreamWaitEvent(l.stream, c->film_order, 0));
         pg_launch_film(l.stream, g, sc, pv, c->d_band_pixels.as<uint32_t>(), l.pb, l.np, l.nl, c->film.as<float4>(),
                        c->film_sq.as<float4>(), c->aov_albedo.as<float4>(), c->aov_normal.as<float4>());
+        if (c->filtered)  // same chunk, same rows (the tail, when it ran, left them as the bounce launches do)
+            launchFilmFiltered(c, l.stream, g, sc, pv, c->d_band_pixels.as<uint32_t>(), l.pb, l.np, l.nl,
+                               sample_offset + l.layer0);
         if (rec) {
             // every slot can emit at most max_vertices records; grow the buffer (lanes idle) when the
             // bound could overflow it
@@ -2310,6 +2455,8 @@ pg_status pg_comm_reduce_film(void *ctx, int32_t root) {
         NCCLC(c, ncclReduce(c->aov_albedo.p, c->aov_albedo.p, nf, ncclFloat32, ncclSum, root, c->comm, c->stream));
         NCCLC(c, ncclReduce(c->aov_normal.p, c->aov_normal.p, nf, ncclFloat32, ncclSum, root, c->comm, c->stream));
     }
+    // the filtered sums overlap at tile borders; integer sums are exact in any order
+    if (c->filtered) NCCLC(c, ncclReduce(c->film_acc.p, c->film_acc.p, nf, ncclInt64, ncclSum, root, c->comm, c->stream));
     NCCLC(c, ncclGroupEnd());
     HIPC(c, hipStreamSynchronize(c->stream));
     return PG_OK;
@@ -2465,6 +2612,7 @@ pg_status pg_reset_film(void *ctx) {
         HIPC(c, hipMemsetAsync(c->aov_albedo.p, 0, fb, c->stream));
         HIPC(c, hipMemsetAsync(c->aov_normal.p, 0, fb, c->stream));
     }
+    if (c->filtered) HIPC(c, hipMemsetAsync(c->film_acc.p, 0, fb * 2, c->stream));
     HIPC(c, hipStreamSynchronize(c->stream));
     return PG_OK;
 }

@@ -194,6 +194,27 @@ void pg_launch_ray_sort(hipStream_t s, Queue q, uint32_t max_shard, uint32_t *so
 void pg_launch_film(hipStream_t s, const GParams &g, const SceneDev &sc, const PathDev &p, const uint32_t *local_pixels,
                     uint32_t pix_begin, uint32_t npix, uint32_t nlayers, float4 *film_rgbw, float4 *film_sumsq,
                     float4 *aov_albedo = nullptr, float4 *aov_normal = nullptr);
+// Reconstruction-filtered film (pg_set_rfilter): the filter's table and the fixed-point sums it is splatted into
+struct FilmFilter {
+    float radius, scale;           // scale = 31 / radius in float32 (ReconstructionFilter::m_scaleFactor)
+    int32_t border;                // ceil(radius - 0.5) (m_borderSize)
+    uint32_t tile;                 // pg_config.tile_size
+    const float *values;           // 32 table entries
+    unsigned long long *acc;       // width * height * 4 two's-complement sums in units of 2^-28
+    const uint32_t *tile_first;    // local tile k holds the local pixels [tile_first[k], tile_first[k + 1])
+    const uint2 *tile_origin;      // its first pixel (x, y)
+};
+// LDS bytes of k_film_filtered's padded tile: (tile + 2 border)^2 x 4 int64
+inline size_t pg_film_filter_lds_bytes(uint32_t tile, int32_t border) {
+    const size_t pw = (size_t)tile + 2 * (size_t)border;
+    return pw * pw * 32;
+}
+// after pg_launch_film for the same chunk; sample_base: the sample index of the chunk's first layer.
+// ntiles > 0: the LDS variant over the local tiles [tile0, tile0 + ntiles) the chunk's pixels lie in;
+// ntiles = 0: the direct variant (one thread per sample, global adds).  Both give the same sums.
+void pg_launch_film_filtered(hipStream_t s, const GParams &g, const SceneDev &sc, const PathDev &p, const FilmFilter &f,
+                             const uint32_t *local_pixels, uint32_t pix_begin, uint32_t npix, uint32_t nlayers,
+                             uint32_t sample_base, uint32_t tile0, uint32_t ntiles);
 // unit-level environment-emitter queries (pg_envmap_query)
 void pg_launch_envmap_query(hipStream_t s, const SceneDev &sc, int op, const float *in, uint32_t n, float *out);
 // p.pinfo == nullptr: the vertex count of slot i is bits(p.rad[i].w) (volpath items)

@@ -1146,8 +1146,22 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PG_
     }
 }
 
+// the sample the film takes from item i of a chunk (ProgressiveMonteCarloIntegrator::renderBlock clamp +
+// ImageBlock::put validity check); false: put rejects it.  Shared by k_film and k_film_filtered.
+__device__ __forceinline__ bool filmSample(const GParams &g, const SceneDev &sc, const PathDev &p, size_t i, float4 &L) {
+    L = p.rad[i];
+    if (sc.env && p.hit) L = envHitRadiance(L, p.hit[i]);  // surface path (volpath: no hit)
+    float m = fmaxf(L.x, fmaxf(L.y, L.z));
+    if (m > g.max_component_value) {
+        float s = g.max_component_value / m;
+        L.x *= s;
+        L.y *= s;
+        L.z *= s;
+    }
+    return isfinite(L.x) && isfinite(L.y) && isfinite(L.z) && L.x >= 0 && L.y >= 0 && L.z >= 0;
+}
+
 // film: box-filtered accumulation of every layer's sample into its pixel, in sample order
-// (ProgressiveMonteCarloIntegrator::renderBlock clamp + ImageBlock::put validity check)
 __global__ __launch_bounds__(256) void k_film(GParams g, SceneDev sc, PathDev p, const uint32_t *__restrict__ local_pixels,
                                               uint32_t pix_begin, uint32_t npix, uint32_t nlayers,
                                               float4 *__restrict__ film, float4 *__restrict__ sumsq,
@@ -1176,17 +1190,8 @@ __global__ __launch_bounds__(256) void k_film(GParams g, SceneDev sc, PathDev p,
     }
     float4 a = film[pix], q = sumsq[pix];
     for (uint32_t l = 0; l < nlayers; ++l) {
-        float4 L = p.rad[(size_t)l * npix + lp];
-        if (sc.env && p.hit) L = envHitRadiance(L, p.hit[(size_t)l * npix + lp]);  // surface path (volpath: no hit)
-        float m = fmaxf(L.x, fmaxf(L.y, L.z));
-        if (m > g.max_component_value) {
-            float s = g.max_component_value / m;
-            L.x *= s;
-            L.y *= s;
-            L.z *= s;
-        }
-        bool okv = isfinite(L.x) && isfinite(L.y) && isfinite(L.z) && L.x >= 0 && L.y >= 0 && L.z >= 0;
-        if (!okv) continue;
+        float4 L;
+        if (!filmSample(g, sc, p, (size_t)l * npix + lp, L)) continue;
         a.x += L.x;
         a.y += L.y;
         a.z += L.z;
@@ -1197,6 +1202,89 @@ __global__ __launch_bounds__(256) void k_film(GParams g, SceneDev sc, PathDev p,
     }
     film[pix] = a;
     sumsq[pix] = q;
+}
+
+// ---- reconstruction-filtered film (pg_set_rfilter): ImageBlock::put (imageblock.h:151-196) over the whole image
+// with the filter's 32-entry table (rfilter.h:76-77), every tap added as a signed 2^-28 fixed-point integer, so
+// the sums do not depend on the order, the chunking or the launch variant (pg_capi.h "filtered film").
+// One tap's add: to the block's LDS tile when `lds` is set and the tap lies inside it, else to the global sums.
+__device__ __forceinline__ void filterAdd(unsigned long long *acc, unsigned long long *lds, uint32_t width, int x, int y,
+                                          int lx0, int ly0, int pw, int c, long long v) {
+    if (v == 0) return;
+    const int ix = x - lx0, iy = y - ly0;
+    if (lds && ix >= 0 && iy >= 0 && ix < pw && iy < pw) atomicAdd(lds + (size_t)c * pw * pw + iy * pw + ix, (unsigned long long)v);
+    else atomicAdd(acc + ((size_t)y * width + x) * 4 + c, (unsigned long long)v);
+}
+// one sample's splat; the jitter is the camera's (k_camera / volCamera: dimension 0 of the path's stream).
+// Float32 without contraction, then exact products in double (pg_capi.h spells out each step).
+__device__ __forceinline__ void filterSplat(const GParams &g, const FilmFilter &f, const float *tab, uint32_t pix,
+                                            uint32_t sample, float4 L, unsigned long long *lds, int lx0, int ly0, int pw) {
+#pragma clang fp contract(off)
+    float jx, jy;
+    rng2(rngKey(pix, g.seed), sample, 0, jx, jy);
+    const float px = (float)(pix % g.width) + jx, py = (float)(pix / g.width) + jy;
+    const float posx = px - 0.5f, posy = py - 0.5f;
+    const int xa = max((int)ceilf(posx - f.radius), 0), xb = min((int)floorf(posx + f.radius), (int)g.width - 1);
+    const int ya = max((int)ceilf(posy - f.radius), 0), yb = min((int)floorf(posy + f.radius), (int)g.height - 1);
+    for (int y = ya; y <= yb; ++y) {
+        const float wy = tab[(int)fminf(fabsf(((float)y - posy) * f.scale), 31.0f)];
+        for (int x = xa; x <= xb; ++x) {
+            const float wx = tab[(int)fminf(fabsf(((float)x - posx) * f.scale), 31.0f)];
+            const float w = wx * wy;
+            if (w == 0.0f) continue;  // every add would be an exact zero
+            const double dw = (double)w;
+            filterAdd(f.acc, lds, g.width, x, y, lx0, ly0, pw, 0, __double2ll_rn(dw * (double)L.x * 268435456.0));
+            filterAdd(f.acc, lds, g.width, x, y, lx0, ly0, pw, 1, __double2ll_rn(dw * (double)L.y * 268435456.0));
+            filterAdd(f.acc, lds, g.width, x, y, lx0, ly0, pw, 2, __double2ll_rn(dw * (double)L.z * 268435456.0));
+            filterAdd(f.acc, lds, g.width, x, y, lx0, ly0, pw, 3, __double2ll_rn(dw * 268435456.0));
+        }
+    }
+}
+// LDS = true: block b takes the chunk's pixels of local tile tile0 + b for all the chunk's layers and stages its
+// taps in a (tile + 2 border)^2 x 4 int64 tile (channel-major: neighbouring pixels' sums sit 8 B apart, so a
+// wave's adds spread over the banks), then adds every non-zero entry to the global sums once.  A tap outside
+// the padded tile (float rounding at pos +- radius can reach one pixel past the border) goes straight to the
+// global sums.  LDS = false: one thread per sample and global adds only (tiles too large for 64 KiB of LDS).
+template <bool LDS>
+__global__ __launch_bounds__(256) void k_film_filtered(GParams g, SceneDev sc, PathDev p, FilmFilter f,
+                                                       const uint32_t *__restrict__ local_pixels, uint32_t pix_begin,
+                                                       uint32_t npix, uint32_t nlayers, uint32_t sample_base,
+                                                       uint32_t tile0) {
+    extern __shared__ unsigned long long tile_acc[];
+    __shared__ float tab[32];
+    if (threadIdx.x < 32) tab[threadIdx.x] = f.values[threadIdx.x];
+    if (LDS) {
+        const int pw = (int)f.tile + 2 * f.border, pp = pw * pw;
+        for (int e = threadIdx.x; e < 4 * pp; e += blockDim.x) tile_acc[e] = 0;
+        __syncthreads();
+        const uint32_t t = tile0 + blockIdx.x;
+        const uint32_t lo = max(f.tile_first[t], pix_begin), hi = min(f.tile_first[t + 1], pix_begin + npix);
+        const uint32_t cnt = hi > lo ? hi - lo : 0;
+        const uint2 org = f.tile_origin[t];
+        const int lx0 = (int)org.x - f.border, ly0 = (int)org.y - f.border;
+        for (uint32_t i = threadIdx.x; i < cnt * nlayers; i += blockDim.x) {
+            const uint32_t layer = i / cnt, lp = (lo - pix_begin) + (i - layer * cnt);
+            float4 L;
+            if (!filmSample(g, sc, p, (size_t)layer * npix + lp, L)) continue;
+            filterSplat(g, f, tab, local_pixels[pix_begin + lp], sample_base + layer, L, tile_acc, lx0, ly0, pw);
+        }
+        __syncthreads();
+        for (int e = threadIdx.x; e < 4 * pp; e += blockDim.x) {
+            const unsigned long long v = tile_acc[e];
+            if (!v) continue;
+            const int c = e / pp, q = e - c * pp, x = lx0 + q % pw, y = ly0 + q / pw;
+            if (x >= 0 && y >= 0 && x < (int)g.width && y < (int)g.height)
+                atomicAdd(f.acc + ((size_t)y * g.width + x) * 4 + c, v);
+        }
+    } else {
+        __syncthreads();
+        const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
+        if (slot >= npix * nlayers) return;
+        const uint32_t layer = slot / npix, lp = slot - layer * npix;
+        float4 L;
+        if (!filmSample(g, sc, p, slot, L)) return;
+        filterSplat(g, f, tab, local_pixels[pix_begin + lp], sample_base + layer, L, nullptr, 0, 0, 0);
+    }
 }
 
 // training records of finished paths: radiance along wo_i = (L_final - L_i) / T_i (channel-wise)
@@ -1707,6 +1795,18 @@ void pg_launch_film(hipStream_t s, const GParams &g, const SceneDev &sc, const P
     if (!npix) return;
     hipLaunchKernelGGL(k_film, dim3(blocks(npix, 256)), dim3(256), 0, s, g, sc, p, local_pixels, pix_begin, npix, nlayers,
                        film_rgbw, film_sumsq, aov_albedo, aov_normal);
+}
+void pg_launch_film_filtered(hipStream_t s, const GParams &g, const SceneDev &sc, const PathDev &p, const FilmFilter &f,
+                             const uint32_t *local_pixels, uint32_t pix_begin, uint32_t npix, uint32_t nlayers,
+                             uint32_t sample_base, uint32_t tile0, uint32_t ntiles) {
+    if (!npix || !nlayers) return;
+    if (ntiles) {  // the LDS tile; the caller checked pg_film_filter_lds_bytes against the 64 KiB limit
+        hipLaunchKernelGGL(k_film_filtered<true>, dim3(ntiles), dim3(256), pg_film_filter_lds_bytes(f.tile, f.border), s, g,
+                           sc, p, f, local_pixels, pix_begin, npix, nlayers, sample_base, tile0);
+    } else {
+        hipLaunchKernelGGL(k_film_filtered<false>, dim3(blocks(npix * nlayers, 256)), dim3(256), 0, s, g, sc, p, f,
+                           local_pixels, pix_begin, npix, nlayers, sample_base, 0u);
+    }
 }
 
 // op 0: sampleDirect from the bounding-sphere centre (in: n x 2 samples; out n x 8: d, pdf, value/pdf, dist)

@@ -65,6 +65,29 @@ def rough_transmittance(distribution, alpha, eta):
     return table, fdr.value
 
 
+_RFILTERS = {"box": capi.PG_RFILTER_BOX, "tent": capi.PG_RFILTER_TENT, "gaussian": capi.PG_RFILTER_GAUSSIAN}
+
+
+def rfilter_table(name, stddev=0.5):
+    """The reference's discretised reconstruction filter (pg_rfilter_table): (radius, 32 float32 values) of
+    "box", "tent" or "gaussian" (stddev).  Host-only, no device needed."""
+    if name not in _RFILTERS:
+        raise ValueError(f"no reconstruction filter table for {name!r} (box, tent, gaussian)")
+    lib = library()
+    values = np.zeros(32, np.float32)
+    radius = C.c_float()
+    st = lib.pg_rfilter_table(_RFILTERS[name], float(stddev), C.byref(radius), _p(values))
+    if st != capi.PG_OK:
+        raise PGError(st, lib.pg_last_error(None).decode())
+    return radius.value, values
+
+
+def develop(rgbw):
+    """hdrfilm's division by the weight channel: sum w L / sum w per pixel, 0 where sum w = 0; (H, W, 3)."""
+    w = rgbw[..., 3:4]
+    return np.where(w != 0, rgbw[..., :3] / np.where(w != 0, w, 1), 0).astype(np.float32)
+
+
 class Device:
     """One pg_ctx: a render context bound to one HIP device and one image-tile shard."""
 
@@ -228,6 +251,26 @@ class Device:
     def reset_film(self):
         self._chk(self.lib.pg_reset_film(self.h))
 
+    def set_rfilter(self, name_or_table, stddev=0.5):
+        """pg_set_rfilter: "box" / "tent" / "gaussian" (stddev), a (radius, 32 values) table, or None (off).
+        Before the first render pass."""
+        if name_or_table is None:
+            self._chk(self.lib.pg_set_rfilter(self.h, 0.0, None))
+            return
+        radius, values = (rfilter_table(name_or_table, stddev) if isinstance(name_or_table, str) else name_or_table)
+        values = np.ascontiguousarray(values, np.float32)
+        if values.shape != (32,):
+            raise ValueError("a reconstruction filter table has 32 values")
+        self._chk(self.lib.pg_set_rfilter(self.h, float(radius), _p(values)))
+
+    def read_film_filtered(self, raw=False):
+        """The filtered film (pg_read_film_filtered), (H, W, 4): sum w r, g, b and sum w as float32, or with
+        raw=True the int64 sums in units of 2^-28."""
+        W, H = self.scene.width, self.scene.height
+        out = np.zeros((H, W, 4), np.int64 if raw else np.float32)
+        self._chk(self.lib.pg_read_film_filtered(self.h, None if raw else _p(out), _p(out) if raw else None))
+        return out
+
     def read_aovs(self):
         """Denoiser feature sums (pg_config.aovs = 1): (albedo rgb + count, normal xyz + 0), (H, W, 4) each."""
         W, H = self.scene.width, self.scene.height
@@ -345,6 +388,15 @@ class ProgressivePathTracer:
         self.max_render_time = float(props.get("maxRenderTime", -1.0))
         self.rendered_spp = 0
         self.render_seconds = 0.0
+        # reconstruction filter: "box", "tent", "gaussian" (with `stddev`) or "scene" (what the loaded scene's
+        # film carries, scene.rfilter); absent: no filtered film.  After render(), `filtered` holds the
+        # filtered sums (H, W, 4) and `developed` the image sum w L / sum w (H, W, 3).
+        self.rfilter = props.get("rfilter")
+        if self.rfilter is not None and self.rfilter not in ("scene",) + tuple(_RFILTERS):
+            raise ValueError(f"rfilter must be box, tent, gaussian or scene, not {self.rfilter!r}")
+        self.stddev = float(props.get("stddev", 0.5))
+        self.filtered = None
+        self.developed = None
         self.dev = None
         self.progression = 0
         self.sample_offset = 0
@@ -353,6 +405,11 @@ class ProgressivePathTracer:
     def preprocess(self, scene):
         self.dev = Device(self.cfg)
         self.dev.upload(scene)
+        if self.rfilter == "scene":
+            name, stddev = getattr(scene, "rfilter", None) or ("gaussian", 0.5)  # film.cpp:93: the default
+            self.dev.set_rfilter(name, stddev)
+        elif self.rfilter is not None:
+            self.dev.set_rfilter(self.rfilter, self.stddev)
         self.progression = 0
         self.sample_offset = 0
         return True
@@ -394,8 +451,14 @@ class ProgressivePathTracer:
             self.rendered_spp = passes * self.spp_per_progression
         self.render_seconds = time.perf_counter() - t0
         rgbw, sq = self.dev.read_film()
+        if self.rfilter is not None:
+            self.filtered = self.dev.read_film_filtered()
         if getattr(self.dev.scene, "mirror_x", False):  # a mirrored sensor (e.g. <scale x="-1"/> in toWorld)
             rgbw, sq = rgbw[:, ::-1].copy(), sq[:, ::-1].copy()
+            if self.filtered is not None:
+                self.filtered = self.filtered[:, ::-1].copy()
+        if self.filtered is not None:
+            self.developed = develop(self.filtered)
         return rgbw, sq
 
     def _render_time_sharded(self, t0):

@@ -12,7 +12,7 @@ adapter's flatten() produces from Scene::getShapes()/getBSDFs() (INTEGRATION.md)
   integrator        any type: (type, properties) returned for the caller (ProgressivePathTracer props)
   sensor            perspective: fov, fovAxis (x, y, diagonal, smaller, larger), nearClip, farClip,
                     toWorld (a mirrored camera, e.g. <scale x="-1"/>, sets Scene.mirror_x);
-                    sampler sampleCount; film width / height (the filter is always the 1-px box)
+                    sampler sampleCount; film width / height and rfilter (box, tent, gaussian: recorded as Scene.rfilter)
   bsdf              diffuse, conductor, roughconductor (material Cu / Al / Au / none, or eta + k),
                     dielectric, roughdielectric, plastic, roughplastic (intIOR / extIOR by value or
                     by name: src/bsdfs/ior.h), twosided, null; distribution beckmann / ggx
@@ -105,6 +105,9 @@ class _Loader:
         self.media = []  # homogeneous media in declaration order: (sigma_t, albedo rgb, g); built in finish()
         self.out = XMLScene()
         self.sc = scenes.Scene()
+        # the film's reconstruction filter (name, stddev); Film::Film's default when the scene names none
+        # (film.cpp:93).  Only recorded: an integrator applies it when asked to (rfilter="scene").
+        self.sc.rfilter = ("gaussian", 0.5)
         self.mat_index = {}  # id(pg_material) -> scene material index
 
     # -- helpers
@@ -463,6 +466,14 @@ class _Loader:
             if c.tag == "film":
                 fp = self.props(c)
                 W, H = int(fp.get("width", W)), int(fp.get("height", H))
+                for f in c:
+                    if f.tag == "rfilter":
+                        ft = self.attr(f, "type")
+                        if ft not in ("box", "tent", "gaussian"):
+                            raise NotImplementedError(f"<rfilter type=\"{ft}\">: no filter table (box, tent and "
+                                                      "gaussian are restated; pass Mitsuba's own table to "
+                                                      "Device.set_rfilter)")
+                        self.sc.rfilter = (ft, float(self.props(f).get("stddev", 0.5)))
             elif c.tag == "sampler":
                 sp = self.props(c)
                 self.out.spp = int(sp.get("sampleCount", 4))

@@ -122,6 +122,17 @@ public:
         m_flat = flatten(scene);  // TriMesh arrays, BSDFs, emitters (area + environment), media, camera
         m_flat.bind();            // the descriptor's pointers into this copy's arrays
         check(pg_upload_scene(m_ctx, &m_flat.desc));
+        // the film's reconstruction filter: any separable filter through its own discretised table
+        // (rfilter.h:76-77); the box keeps the per-pixel film
+        const ReconstructionFilter *rf = scene->getSensor()->getFilm()->getReconstructionFilter();
+        m_filtered = rf && rf->getClass()->getName() != "BoxFilter";
+        if (m_filtered) {
+            float values[32];
+            const float radius = (float) rf->getRadius();
+            // entry i at the middle of its bin, so that float rounding cannot select a neighbouring entry
+            for (int i = 0; i < 32; ++i) values[i] = (float) rf->evalDiscretized(radius * (i + 0.5f) / 31);
+            check(pg_set_rfilter(m_ctx, radius, values));
+        }
         if (m_cfg.world_size > 1) initComm();
         // Li() / renderBlock() / E() keep working through Mitsuba's own CPU integrator (not guided)
         Properties pp(m_cfg.integrator == PG_INTEGRATOR_VOLPATH ? "volpath" : "path");
@@ -251,12 +262,24 @@ public:
             denoiser->denoise();
             if (!m_denoiserFile.empty()) denoiser->storeBuffers(m_denoiserFile);
         }
+        // the filtered film (sum w L, sum w) of the final render; the denoiser's inputs and the inverse-variance
+        // combination stay per-pixel statistics, so their images keep the per-pixel means
+        const bool filtered = m_filtered && !m_denoise && (m_sampleCombination != "inversevar" || m_iterationFilms.empty());
+        std::vector<float> frgbw;
+        if (filtered) {
+            frgbw.resize(4 * npix);
+            check(pg_read_film_filtered(m_ctx, frgbw.data(), NULL));
+        }
         ref<ImageBlock> block = new ImageBlock(Bitmap::ESpectrumAlphaWeight, size, NULL);
         for (int y = 0; y < size.y; ++y)
             for (int x = 0; x < size.x; ++x) {
                 Spectrum s;
                 if (m_denoise) {
                     s = denoiser->get(y * size.x + x);
+                } else if (filtered) {                           // hdrfilm's division by the weight channel
+                    const float *p = &frgbw[4 * src(x, y)];
+                    if (p[3] != 0) s.fromLinearRGB(p[0] / p[3], p[1] / p[3], p[2] / p[3]);
+                    else s = Spectrum(0.0f);
                 } else {
                     const float *p = &rgbw[4 * src(x, y)];
                     Float w = std::max(p[3], 1.0f);
@@ -402,6 +425,7 @@ protected:
     int m_mediumResolution;
     std::string m_sampleCombination, m_denoiserFile;
     bool m_denoise = false;
+    bool m_filtered = false;                                    // the film's filter is not the box: pg_set_rfilter
     struct FilmSums { std::vector<float> rgbw, sumsq; };
     std::vector<FilmSums> m_iterationFilms;                     // sampleCombination = "inversevar"
 };
