@@ -401,6 +401,18 @@ pg_status pg_get_culled(void *ctx, uint64_t *count);
  * PG_NO_DOOM_PROBE=1 or PG_NO_PATH_CULL=1 in the environment, and for scenes with an environment emitter.  A
  * read-only entry point like pg_get_culled: pg_stats keeps its ABI 12 layout. */
 pg_status pg_get_probes(void *ctx, uint64_t *count);
+/* Path integrator: next-event shadow rays since create that the shading kernels resolved as occluded against the
+ * learned blocker list, before the ray was stored or queued.  The recording passes count, per triangle, the shadow
+ * rays it blocked; after each of them up to 8 triangles that each blocked at least 1/64 of the counted rays are listed,
+ * and a later shadow ray that certainly hits one of them (margins on its barycentrics and distance, so the any-hit
+ * walk would agree) is dropped where it would have been written.  Each is still counted in pg_stats.shadow_rays.
+ * Results do not depend on the list.  0 with PG_NO_SHADOW_CULL=1 in the environment, before the first recording
+ * pass, after pg_upload_scene / pg_put_sdtree (the list is emptied) and for scenes with an environment emitter.
+ * A read-only entry point like pg_get_culled: pg_stats keeps its ABI 12 layout. */
+pg_status pg_get_shadow_culled(void *ctx, uint64_t *count);
+/* The current blocker list: *count (<= 8) BVH-order triangle ids in tri_ids[8], most frequent first, and (orig_ids
+ * not NULL) the same triangles' indices in the uploaded scene. */
+pg_status pg_get_blockers(void *ctx, uint32_t *tri_ids, uint32_t *orig_ids, uint32_t *count);
 /* Number of pixels owned by this rank (tile shard). */
 pg_status pg_local_pixel_count(void *ctx, uint64_t *count);
 
@@ -408,6 +420,10 @@ pg_status pg_local_pixel_count(void *ctx, uint64_t *count);
 /* rays: n x 8 floats (o.xyz, tmin, d.xyz, tmax).  hits: n x 4 (t, prim as float bits, u, v);
  * prim = 0xFFFFFFFF for a miss.  any_hit: hits[i*4] = 1 if occluded else 0. */
 pg_status pg_trace_rays(void *ctx, const float *rays, uint64_t n, int32_t any_hit, float *hits);
+/* The shading kernels' blocker test on given rays (n x 8 floats as pg_trace_rays) against the k <= 8 BVH-order
+ * triangles tri_ids, installed as the list for this call only: out[i] = 1 where the test answers "certainly
+ * occluded", else 0.  Wherever it answers 1, pg_trace_rays(any_hit = 1) answers occluded. */
+pg_status pg_blocker_test(void *ctx, const float *rays, uint64_t n, const uint32_t *tri_ids, uint32_t k, uint32_t *out);
 /* The closest hit's full record as the shading kernels build it (fillIntersectionRecord<true>,
  * skdtree.h:343-430: barycentric position, face normal flipped to the shading normal's side, interpolated
  * shading normal, shading frame by computeShadingFrame(n, dpdu = p1 - p0), wi = toLocal(-d)); the unit KAT of

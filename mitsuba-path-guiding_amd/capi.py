@@ -179,6 +179,9 @@ SIGNATURES = [
     ("pg_get_stats", C.c_int32, [VP, C.POINTER(pg_stats)]),
     ("pg_get_culled", C.c_int32, [VP, C.POINTER(C.c_uint64)]),
     ("pg_get_probes", C.c_int32, [VP, C.POINTER(C.c_uint64)]),
+    ("pg_get_shadow_culled", C.c_int32, [VP, C.POINTER(C.c_uint64)]),
+    ("pg_get_blockers", C.c_int32, [VP, VP, VP, C.POINTER(C.c_uint32)]),
+    ("pg_blocker_test", C.c_int32, [VP, VP, C.c_uint64, VP, C.c_uint32, VP]),
     ("pg_local_pixel_count", C.c_int32, [VP, C.POINTER(C.c_uint64)]),
     ("pg_trace_rays", C.c_int32, [VP, VP, C.c_uint64, C.c_int32, VP]),
     ("pg_hit_records", C.c_int32, [VP, VP, C.c_uint64, VP]),

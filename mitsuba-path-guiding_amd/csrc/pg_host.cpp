@@ -32,10 +32,12 @@ constexpr uint32_t kMaxBounces = 1100;     // > gpu_depth_cap default (1024) + 2
 // [64, 128) shadow-queue shard counts, [128, 640) shard counts of the PG_NUM_CLASSES material-class
 // queues followed by the escaped-ray and the culled-hit counts (PG_CLASS_ROWS rows), [640, 704) shard counts of the
 // probe queue the bounce's shading fills (pg_layout.h "Doom probe")
-constexpr uint32_t kBounceWords = 704;
+constexpr uint32_t kBounceWords = 768;
 constexpr uint32_t kShadowCounts = PG_QSHARDS, kClassCounts = 2 * PG_QSHARDS;
 constexpr uint32_t kProbeCounts = kClassCounts + PG_CLASS_ROWS * PG_QSHARDS;
-static_assert(kProbeCounts + PG_QSHARDS <= kBounceWords, "counter layout");
+// shadow rays the shader resolved against the blocker list (Queue::dropped of the shadow queue)
+constexpr uint32_t kDropCounts = kProbeCounts + PG_QSHARDS;
+static_assert(kDropCounts + PG_QSHARDS <= kBounceWords, "counter layout");
 constexpr uint32_t kCounterWords = kBounceWords * (kMaxBounces + 1);
 // the device's bounce cap (GParams::depth_cap): max_depth + 1 or gpu_depth_cap.  The surface path keeps
 // one counter block per bounce, so its cap is at most kMaxBounces - 2 (pg_create rejects a larger
@@ -132,7 +134,7 @@ uint64_t smallPass() {
 #define PG_PIXEL_BLOCK 8  // local pixel order inside a tile: 8x8 blocks (0: row-major)
 #endif
 #define PG_DEFAULT_LANES 3
-constexpr size_t kTailStats = 5;  // k_tail: segments, escaped, shadow rays, culled, probes
+constexpr size_t kTailStats = 6;  // k_tail: segments, escaped, shadow rays, culled, probes, blocker-resolved shadow rays
 struct Lane {
     hipStream_t stream = nullptr;
     uint32_t P = 0;
@@ -217,6 +219,16 @@ struct Ctx {
     uint32_t num_em_boxes = 0;
     float em_absmax = 0.0f;
     float em_box[PG_EMBOX_MAX][6] = {};
+    // shadow blockers (pg_layout.h "Shadow blockers"): the per-triangle counts of the recording passes and the list
+    // chosen from them (SceneDev::blk); both empty after an upload and after pg_put_sdtree (a new job)
+    DevBuf blk_counts;
+    PinnedBuf h_blk_counts;     // the counts' host copy (learnBlockers)
+    std::vector<float> host_tris, host_shade;  // host copies of tris and tshade: the listed triangles' records
+    bool blk_stopped = false;   // no more counting in this job, the list stays (learnBlockers)
+    uint32_t num_blockers = 0;
+    uint32_t blk_ids[PG_MAX_BLOCKERS] = {}, blk_orig[PG_MAX_BLOCKERS] = {};  // BVH-order and original ids
+    float blk[PG_MAX_BLOCKERS][12] = {};
+    float absmax = 0.0f;  // the scene's largest |coordinate|
     std::vector<GMat> host_mats;
     float scene_lo[3] = {0, 0, 0}, scene_hi[3] = {0, 0, 0};
     // shard
@@ -267,6 +279,7 @@ struct Ctx {
     pg_stats stats{};
     uint64_t culled = 0;  // segments whose hit the tracer culled (pg_get_culled); counted in stats.segments
     uint64_t probes = 0;  // segments answered by an any-hit probe (pg_get_probes); counted in culled or escaped
+    uint64_t shadow_culled = 0;  // shadow rays resolved against the blocker list; counted in stats.shadow_rays
 };
 
 thread_local std::string g_tls_err;
@@ -417,7 +430,57 @@ SceneDev sceneView(const Ctx *c) {
     sc.num_em_boxes = c->num_em_boxes;
     sc.em_absmax = c->em_absmax;
     std::memcpy(sc.em_box, c->em_box, sizeof(sc.em_box));
+    // the blocker list; PG_NO_SHADOW_CULL=1 (or an environment emitter) renders with an empty one (same results)
+    sc.num_blockers = (c->has_env || std::getenv("PG_NO_SHADOW_CULL")) ? 0u : c->num_blockers;
+    sc.absmax = c->absmax;
+    sc.blk_counts = sc.blk_total = nullptr;  // set by the recording passes
+    std::memcpy(sc.blk, c->blk, sizeof(sc.blk));
     return sc;
+}
+
+// a new job on the scene: no blockers, no counts
+pg_status resetBlockers(Ctx *c) {
+    c->num_blockers = 0;
+    c->blk_stopped = false;
+    if (c->blk_counts.p) HIPC(c, hipMemsetAsync(c->blk_counts.p, 0, ((size_t)c->num_tris + 1) * 4, c->stream));
+    return PG_OK;
+}
+// lists the triangles `ids` (BVH order) in blk / blk_ids from the host copies of their TriAccel rows and shading
+// records (no device round trip); triangles too small for the test's margins (pg_ray_hits_blockers) are left out
+pg_status installBlockers(Ctx *c, const uint32_t *ids, uint32_t n, float (*blk)[12], uint32_t *blk_ids, uint32_t *orig,
+                          uint32_t *count) {
+    *count = 0;
+    uint32_t m = 0;
+    for (uint32_t i = 0; i < n && m < PG_MAX_BLOCKERS; ++i) {
+        if (ids[i] >= c->num_tris) return fail(c, PG_ERR_INVALID, "blocker triangle id out of range");
+        float rows[12];
+        for (int r = 0; r < 3; ++r) std::memcpy(rows + 4 * r, &c->host_tris[4 * (size_t)PG_TRI_ROW(ids[i], r)], 16);
+        const float *sh = &c->host_shade[4 * (size_t)PG_TRI_SHADE_STRIDE * ids[i]];
+        pg_blocker_record(rows, sh, sh + 4, sh + 8, ids[i], blk[m]);
+        if (!(blk[m][11] * 32.0f >= c->absmax)) continue;
+        if (orig) std::memcpy(&orig[m], &sh[11], 4);  // the original triangle id (pg_layout.h PG_TRI_SHADE_F4)
+        blk_ids[m++] = ids[i];
+    }
+    *count = m;
+    return PG_OK;
+}
+// after a recording pass: the cumulative counts to the host (pinned; the last word is the number of shadow rays the
+// counts were taken from), the list chosen from them
+pg_status learnBlockers(Ctx *c) {
+    const size_t bytes = ((size_t)c->num_tris + 1) * 4;
+    HIPC(c, c->h_blk_counts.reserve(bytes));
+    const uint32_t *counts = (const uint32_t *)c->h_blk_counts.p;
+    HIPC(c, hipMemcpyAsync(c->h_blk_counts.p, c->blk_counts.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    uint32_t ids[PG_MAX_BLOCKERS];
+    const uint32_t total = counts[c->num_tris];
+    const uint32_t n = pg_select_blockers(counts, c->num_tris, total, ids);
+    if (total >= PG_BLOCKER_COUNT_STOP) c->blk_stopped = true;  // no count exceeds the total
+    // no list from PG_BLOCKER_DECIDE counted rays or more: the light is mostly visible, or the blockers are many.  The
+    // shares will not change, so the job's later recording passes neither count nor read back (the kitchen's training
+    // paid 4-5 % for them)
+    if (n == 0 && total >= PG_BLOCKER_DECIDE) c->blk_stopped = true;
+    return installBlockers(c, ids, n, c->blk, c->blk_ids, c->blk_orig, &c->num_blockers);
 }
 SDDev sdView(const Ctx *c) {
     SDDev s{};
@@ -1100,6 +1163,14 @@ pg_status pg_upload_scene(void *ctx, const pg_scene_desc *d) {
         c->num_em_boxes = pg_emitter_boxes(d->positions, d->indices, triEmitter.data(), nt, d->num_emitters, c->em_box,
                                            &c->em_absmax);
     }
+    c->num_blockers = 0;
+    c->blk_stopped = false;
+    c->absmax = 0.0f;
+    for (size_t i = 0; i < (size_t)3 * d->num_vertices; ++i) c->absmax = std::max(c->absmax, std::fabs(d->positions[i]));
+    HIPC(c, c->blk_counts.alloc(((size_t)nt + 1) * 4));  // the last word: the shadow rays counted
+    HIPC(c, hipMemsetAsync(c->blk_counts.p, 0, ((size_t)nt + 1) * 4, c->stream));
+    c->host_tris = bvh.tris;
+    c->host_shade = shade;
     c->host_mats.clear();
     for (uint32_t m = 0; m < d->num_materials; ++m) c->host_mats.push_back(makeGMat(d->materials[m]));
     // roughplastic: rough-transmittance slice + internal diffuse Fresnel per material
@@ -1937,7 +2008,14 @@ static pg_status renderPass(Ctx *c, uint32_t spp, uint32_t sample_offset, int32_
     g.glossy_prior = c->cfg.glossy_prior;
     g.seed = c->cfg.seed;
     g.depth_cap = deviceDepthCap(c->cfg);
-    const SceneDev sc = sceneView(c);
+    SceneDev sc = sceneView(c);
+    // recording passes count the triangles that block shadow rays (pg_layout.h "Shadow blockers")
+    const bool learn = rec && !c->has_env && g.use_nee && !c->blk_stopped && !std::getenv("PG_NO_SHADOW_CULL");
+
+    if (learn) {
+        sc.blk_counts = c->blk_counts.as<uint32_t>();
+        sc.blk_total = sc.blk_counts + c->num_tris;
+    }
     const SDDev sd = sdView(c);
     const uint32_t maxBounces = std::min<uint32_t>(g.depth_cap + 2, kMaxBounces);
     const bool evt = c->cfg.kernel_timing != 0;  // per-launch HIP events (pg_stats trace/shade/shadow_ms)
@@ -2002,12 +2080,16 @@ static pg_status renderPass(Ctx *c, uint32_t spp, uint32_t sample_offset, int32_
             {
                 c->stats.shadow_rays += l.h_stats[(size_t)kBounceWords * k + kShadowCounts + sh];
                 c->probes += l.h_stats[(size_t)kBounceWords * k + kProbeCounts + sh];
+                // shadow rays the shader resolved: never queued, still shadow rays of the job
+                c->stats.shadow_rays += l.h_stats[(size_t)kBounceWords * k + kDropCounts + sh];
+                c->shadow_culled += l.h_stats[(size_t)kBounceWords * k + kDropCounts + sh];
             }
         c->stats.segments += l.h_tail[0];  // the chunk's tail (k_tail)
         c->stats.escaped += l.h_tail[1];
         c->stats.shadow_rays += l.h_tail[2];
         c->culled += l.h_tail[3];
         c->probes += l.h_tail[4];
+        c->shadow_culled += l.h_tail[5];
         if (std::getenv("PG_DEBUG_COUNTS")) {
             for (uint32_t k = 0; k < l.stats_bounces && k < l.used_prev.size(); ++k) {
                 uint64_t t = 0;
@@ -2162,7 +2244,8 @@ static pg_status renderPass(Ctx *c, uint32_t spp, uint32_t sample_offset, int32_
         classQueues(l, cb, cls);
         const PathDev pv = pathView(&l);
         Queue next = lqueue(l, (l.b & 1) ? l.q1.as<uint32_t>() : l.q0.as<uint32_t>(), cb + kBounceWords);
-        const Queue shq = lqueue(l, l.qs.as<uint32_t>(), cb + kShadowCounts);
+        Queue shq = lqueue(l, l.qs.as<uint32_t>(), cb + kShadowCounts);
+        shq.dropped = cb + kDropCounts;
         const Queue pq = lqueue(l, l.qp.as<uint32_t>(), cb + kProbeCounts);
         const uint32_t nextBound = *std::max_element(shardLive, shardLive + PG_QSHARDS);
         const bool sortNext = raySortEnabled() && nextBound >= kRaySortMinShard;
@@ -2188,7 +2271,7 @@ static pg_status renderPass(Ctx *c, uint32_t spp, uint32_t sample_offset, int32_
         if (fuseRays) return launchTrace(l, &shq, &pq);
         if (evt) ew = nextEvents(&l, KT_SHADOW);
         if (evt) HIPC(c, hipEventRecord(ew.a, l.stream));
-        pg_launch_shadow(l.stream, sc, pv, shq, l.bound);
+        pg_launch_shadow(l.stream, g, sc, pv, shq, l.bound);
         if (g.doom_probe) {  // the probes of this bounce, counted with the closest hits of the trace that follows
             Queue ncls[PG_CLASS_ROWS];
             classQueues(l, cb + kBounceWords, ncls);
@@ -2231,6 +2314,7 @@ static pg_status renderPass(Ctx *c, uint32_t spp, uint32_t sample_offset, int32_
         c->rec_host_count = c->rec_bound = rc;
     }
     HIPC(c, hipStreamSynchronize(c->stream));
+    if (learn && (s = learnBlockers(c))) return s;
     return PG_OK;
 }
 
@@ -2547,6 +2631,7 @@ pg_status pg_put_sdtree(void *ctx, const void *buf, uint64_t size) {
     pgh::SdTree t;
     if (!t.deserialize((const uint8_t *)buf, size)) return fail(c, PG_ERR_INVALID, "pg_put_sdtree: malformed blob");
     c->sd = std::move(t);
+    if (pg_status s = resetBlockers(c)) return s;  // a tree from outside starts a new job: nothing learned carries over
     return uploadSd(c);
 }
 
@@ -2670,6 +2755,23 @@ pg_status pg_get_culled(void *ctx, uint64_t *count) {
     return PG_OK;
 }
 
+pg_status pg_get_shadow_culled(void *ctx, uint64_t *count) {
+    Ctx *c = (Ctx *)ctx;
+    if (!c || !count) return fail(c, PG_ERR_INVALID, "pg_get_shadow_culled: null argument");
+    *count = c->shadow_culled;
+    return PG_OK;
+}
+pg_status pg_get_blockers(void *ctx, uint32_t *tri_ids, uint32_t *orig_ids, uint32_t *count) {
+    Ctx *c = (Ctx *)ctx;
+    if (!c || !tri_ids || !count) return fail(c, PG_ERR_INVALID, "pg_get_blockers: null argument");
+    *count = c->num_blockers;
+    for (uint32_t i = 0; i < c->num_blockers; ++i) {
+        tri_ids[i] = c->blk_ids[i];
+        if (orig_ids) orig_ids[i] = c->blk_orig[i];
+    }
+    return PG_OK;
+}
+
 pg_status pg_local_pixel_count(void *ctx, uint64_t *count) {
     Ctx *c = (Ctx *)ctx;
     if (!c || !count) return fail(c, PG_ERR_INVALID, "pg_local_pixel_count: null argument");
@@ -2692,6 +2794,27 @@ pg_status pg_trace_rays(void *ctx, const float *rays, uint64_t n, int32_t any_hi
                          ovf.as<uint32_t>());
     HIPC(c, hipGetLastError());
     HIPC(c, hipMemcpyAsync(hits, h.p, n * 16, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    return PG_OK;
+}
+
+pg_status pg_blocker_test(void *ctx, const float *rays, uint64_t n, const uint32_t *tri_ids, uint32_t k, uint32_t *out) {
+    Ctx *c = (Ctx *)ctx;
+    if (!c || (!rays && n) || (!out && n) || (!tri_ids && k)) return fail(c, PG_ERR_INVALID, "pg_blocker_test: null argument");
+    if (!c->has_scene) return fail(c, PG_ERR_STATE, "pg_blocker_test: no scene");
+    if (k > PG_MAX_BLOCKERS) return fail(c, PG_ERR_INVALID, "pg_blocker_test: more than PG_MAX_BLOCKERS triangles");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    if (!n) return PG_OK;
+    SceneDev sc = sceneView(c);
+    uint32_t ids[PG_MAX_BLOCKERS];
+    if (pg_status s = installBlockers(c, tri_ids, k, sc.blk, ids, nullptr, &sc.num_blockers)) return s;
+    DevBuf r, o;
+    HIPC(c, r.alloc(n * 32));
+    HIPC(c, o.alloc(n * 4));
+    HIPC(c, hipMemcpyAsync(r.p, rays, n * 32, hipMemcpyHostToDevice, c->stream));
+    pg_launch_blocker_test(c->stream, sc, r.as<float>(), (uint32_t)n, o.as<uint32_t>());
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipMemcpyAsync(out, o.p, n * 4, hipMemcpyDeviceToHost, c->stream));
     HIPC(c, hipStreamSynchronize(c->stream));
     return PG_OK;
 }

@@ -22,6 +22,13 @@ struct SceneDev {
     uint32_t num_em_boxes;
     float em_absmax;        // the boxes' largest |coordinate|
     float em_box[PG_EMBOX_MAX][6];
+    // shadow blockers (pg_layout.h "Shadow blockers"; by value as em_box): the listed records, 0 of them when nothing
+    // qualifies, with an environment emitter or with PG_NO_SHADOW_CULL=1
+    uint32_t num_blockers;
+    float absmax;           // the scene's largest |coordinate|
+    uint32_t *blk_counts;   // per BVH-order triangle: shadow rays it blocked (recording passes; nullptr: not counted)
+    uint32_t *blk_total;    // the shadow rays, occluded or not, that blk_counts was taken from (one word)
+    float blk[PG_MAX_BLOCKERS][12];
 };
 
 // float4 per training vertex: (x, woPdf), (T after the vertex, packed canonical wo), (L snapshot, -),
@@ -110,6 +117,9 @@ struct Queue {
     uint32_t *counts;  // PG_QSHARDS
     uint32_t stride;
     uint16_t *keys = nullptr;  // ray order keys of the entries (k_shade's output queue when rays are sorted)
+    // a counted-only row that goes with the queue (PG_QSHARDS): the shadow queue's rays that shadeOne resolved against
+    // the blocker list and never appended
+    uint32_t *dropped = nullptr;
 };
 // Ray order for the next closest-hit launch (pg_config: PG_RAY_SORT): key = direction octant (3 bits,
 // major) then the Morton code of the origin's cell in an 8^3 grid over the SD-tree cube (9 bits)
@@ -178,12 +188,13 @@ void pg_launch_shade_all(hipStream_t s, const GParams &g, const SceneDev &sc, co
 // `probe` (max_shadow_shard bounds its shards too), counted in class_queues' culled / escaped rows
 void pg_launch_rays(hipStream_t s, const GParams &g, const SceneDev &sc, const PathDev &p, Queue q, uint32_t max_shard,
                     const Queue *class_queues, Queue shq, uint32_t max_shadow_shard, Queue probe);
-void pg_launch_shadow(hipStream_t s, const SceneDev &sc, const PathDev &p, Queue q, uint32_t max_shard);
+void pg_launch_shadow(hipStream_t s, const GParams &g, const SceneDev &sc, const PathDev &p, Queue q, uint32_t max_shard);
 // the probes alone (the unfused launches): hits to class_queues[PG_CLASS_CULLED], misses to [PG_CLASS_ESCAPED]
 void pg_launch_probe(hipStream_t s, const SceneDev &sc, const PathDev &p, Queue probe, uint32_t max_shard,
                      const Queue *class_queues);
 // every remaining path of the queue `q` (its hits already traced) to its end in one launch, each thread
-// looping shade -> shadow ray -> closest hit (k_tail); stats: 5 u64 (segments, escaped, shadow rays, culled, probes)
+// looping shade -> shadow ray -> closest hit (k_tail); stats: 6 u64 (segments, escaped, shadow rays, culled, probes,
+// shadow rays resolved against the blocker list -- also counted in shadow rays)
 void pg_launch_tail(hipStream_t s, const GParams &g, const SceneDev &sc, const SDDev &sd, const PathDev &p, Queue q,
                     uint32_t max_shard, unsigned long long *stats);
 // counting sort of every shard of `q` by its keys into sorted_items (same shard layout and counts):
@@ -257,6 +268,8 @@ void pg_launch_medium_query(hipStream_t s, const GMedium *medium, int op, const 
                             uint32_t n, float *out);
 void pg_launch_trace_rays(hipStream_t s, const SceneDev &sc, const float *rays, uint32_t n, int any, float *hits,
                           uint32_t *ovf);
+// unit-level blocker test (pg_blocker_test): out[i] = 1 where pg_ray_hits_blockers answers for ray i against sc.blk
+void pg_launch_blocker_test(hipStream_t s, const SceneDev &sc, const float *rays, uint32_t n, uint32_t *out);
 // words of traversal-stack overflow storage for a launch of max_threads (0 = persistent grid)
 size_t pg_stack_overflow_words(uint64_t max_threads);
 // threads pg_launch_trace_rays launches for n rays (size its overflow ring with this)

@@ -379,34 +379,63 @@ __device__ __forceinline__ float shadowTmin(float4 o) {
     return kEpsilon * fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fabsf(o.z));
 }
 
+template <class T>
+__device__ __forceinline__ void waveKeyedAdd(T *base, uint32_t key, T v, bool valid);
+// the rows (a block's share of a queue shard) whose shadow rays the recording passes count (pg_layout.h PG_BLOCKER_SAMPLE)
+__device__ __forceinline__ bool blockerRowCounted(uint32_t row) { return row % PG_BLOCKER_SAMPLE == 0; }
 // any hit for queued shadow rays; unoccluded -> add the NEE contribution to L (and to the
 // training vertex's radiance snapshot, so its record excludes light arriving from elsewhere)
+// COUNT (recording passes without an environment emitter, pg_layout.h "Shadow blockers"): every occluded ray adds one
+// to sc.blk_counts[the triangle the walk accepted], wave-aggregated by triangle (a few triangles take nearly all the
+// counts).  An instantiation of its own, so the final render's kernels carry none of it.
+// an unoccluded shadow ray's contribution (sh_c) to its path's L and to its training vertex's snapshot
+__device__ __forceinline__ void shadowAdd(const PathDev &p, uint32_t slot) {
+    float4 c = ldS(&p.sh_c[slot]);
+    float4 L = ldS(&p.rad[slot]);
+    stS(&p.rad[slot], make_float4(L.x + c.x, L.y + c.y, L.z + c.z, L.w));
+    uint32_t vi = __float_as_uint(c.w);
+    if (vi != 0xFFFFFFFFu) {
+        float4 *vl = p.vtx + ((size_t)vi * p.vtxP + slot) * PG_VTX_F4 + 2;
+        float4 a = *vl;
+        *vl = make_float4(a.x + c.x, a.y + c.y, a.z + c.z, a.w);
+    }
+}
+template <bool COUNT>
 __device__ __forceinline__ void shadowRows(const SceneDev &sc, const PathDev &p, const Queue &q, uint32_t bid,
                                            uint32_t nblk, const WStack &stk) {
     const uint32_t s = bid & (PG_QSHARDS - 1);
     const uint32_t n = q.counts[s];
     const uint32_t *items = q.items + (size_t)s * q.stride;
+    if constexpr (COUNT) {
+        // block-uniform loop bound: whole waves reach the keyed add together
+        for (uint32_t base = (bid / PG_QSHARDS) * TRACE_BLOCK; base < n; base += nblk / PG_QSHARDS * TRACE_BLOCK) {
+            const uint32_t i = base + threadIdx.x;
+            uint32_t tri = 0xFFFFFFFFu;
+            if (i < n) {
+                const uint32_t slot = items[i];
+                const float4 o = ldS(&p.ray_o[slot]), d = ldS(&p.sh_d[slot]);
+                if (!occluded(sc, xyz(o), xyz(d), shadowTmin(o), d.w, stk, tri)) shadowAdd(p, slot);
+            }
+            if (blockerRowCounted(base / TRACE_BLOCK)) {  // pg_layout.h PG_BLOCKER_SAMPLE
+                waveKeyedAdd<uint32_t>(sc.blk_counts, tri, 1u, tri != 0xFFFFFFFFu);
+                const unsigned long long rays = __ballot(i < n);
+                if ((threadIdx.x & 63) == 0 && rays) atomicAdd(sc.blk_total, (uint32_t)__popcll(rays));
+            }
+        }
+        return;
+    }
     for (uint32_t i = (bid / PG_QSHARDS) * TRACE_BLOCK + threadIdx.x; i < n; i += nblk / PG_QSHARDS * TRACE_BLOCK) {
         uint32_t slot = items[i];
         // the shadow ray starts at the shading point, which is also the extension ray's origin
         float4 o = ldS(&p.ray_o[slot]), d = ldS(&p.sh_d[slot]);
-        if (!occluded(sc, xyz(o), xyz(d), shadowTmin(o), d.w, stk)) {
-            float4 c = ldS(&p.sh_c[slot]);
-            float4 L = ldS(&p.rad[slot]);
-            stS(&p.rad[slot], make_float4(L.x + c.x, L.y + c.y, L.z + c.z, L.w));
-            uint32_t vi = __float_as_uint(c.w);
-            if (vi != 0xFFFFFFFFu) {
-                float4 *vl = p.vtx + ((size_t)vi * p.vtxP + slot) * PG_VTX_F4 + 2;
-                float4 a = *vl;
-                *vl = make_float4(a.x + c.x, a.y + c.y, a.z + c.z, a.w);
-            }
-        }
+        if (!occluded(sc, xyz(o), xyz(d), shadowTmin(o), d.w, stk)) shadowAdd(p, slot);
     }
 }
 
+template <bool COUNT>
 __global__ __launch_bounds__(TRACE_BLOCK) void k_shadow(SceneDev sc, PathDev p, Queue q) {
     __shared__ uint32_t stack[2 * WIDE_LDS_STACK * TRACE_BLOCK];
-    shadowRows(sc, p, q, blockIdx.x, gridDim.x, threadWideStack(stack, p.stack_ovf));
+    shadowRows<COUNT>(sc, p, q, blockIdx.x, gridDim.x, threadWideStack(stack, p.stack_ovf));
 }
 
 // Doom probe (pg_layout.h): does the doomed ray (o, d) hit anything?  The closest-hit walk's own 4-wide nodes, padded
@@ -458,10 +487,11 @@ static_assert(2 * WIDE_LDS_STACK >= LDS_STACK, "k_rays / k_trace_rays share one 
 #ifndef PG_RAYS_TRACE_FIRST
 #define PG_RAYS_TRACE_FIRST 1
 #endif
-template <bool ENV>
 #ifndef PG_RAYS_WAVES
 #define PG_RAYS_WAVES 8
 #endif
+// COUNT: the recording passes' instantiation, whose shadow rows count blockers (shadowRows)
+template <bool ENV, bool COUNT = false>
 __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PG_RAYS_WAVES))) void k_rays(GParams g, SceneDev sc, PathDev p, Queue q, ClassQueues cqs,
                                                       Queue shq, uint32_t shadow_blocks, Queue pq, uint32_t probe_blocks) {
     // >= LDS_STACK words per thread (twice that for the paired walks)
@@ -474,7 +504,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PG_
 #if PG_RAYS_TRACE_FIRST  // the costlier closest-hit blocks dispatched first (profiles/r03zg_rays_order_ab)
     const uint32_t trace_blocks = gridDim.x - probe_blocks - shadow_blocks;
     if (blockIdx.x >= trace_blocks) {
-        shadowRows(sc, p, shq, blockIdx.x - trace_blocks, shadow_blocks, threadWideStack(stack, p.stack_ovf));
+        shadowRows<COUNT>(sc, p, shq, blockIdx.x - trace_blocks, shadow_blocks, threadWideStack(stack, p.stack_ovf));
     } else {
         // the 4-wide BVH's breadth-first top levels in LDS (PG_RAYS_LDS_TOP, A/B; round 5 re-measure of the
         // round-2 tile on the 64-B nodes)
@@ -496,7 +526,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PG_
     }
 #else
     if (blockIdx.x < shadow_blocks)
-        shadowRows(sc, p, shq, blockIdx.x, shadow_blocks, threadWideStack(stack, p.stack_ovf));
+        shadowRows<COUNT>(sc, p, shq, blockIdx.x, shadow_blocks, threadWideStack(stack, p.stack_ovf));
     else
         traceRows<ENV, false, false>(g, sc, p, q, cqs, nullptr, blockIdx.x - shadow_blocks,
                               gridDim.x - probe_blocks - shadow_blocks, threadStack(stack, p.stack_ovf), nullptr, 0);
@@ -587,7 +617,7 @@ extern "C" int pg_debug_watch_read(float *out, uint32_t max, uint32_t *n) {
 template <int MODEL, bool CAN_GUIDE, bool ENV>
 __device__ __forceinline__ void shadeOne(const GParams &g, const SceneDev &sc, const SDDev &sd, const PathDev &p,
                                          uint32_t slot, const GMat *mats, bool wantKey, bool &alive, bool &shadow,
-                                         bool &probe, uint32_t &rkey) {
+                                         bool &probe, uint32_t &rkey, uint32_t &blocked) {
     bool dirtyL = false;
     f3 L = mk1(0.f);
     // the watch build logs every vertex with its own roulette draw, as the oracle does
@@ -755,7 +785,16 @@ __device__ __forceinline__ void shadeOne(const GParams &g, const SceneDev &sc, c
                     neeEmPdf = emPdf;
                     neeV = T * value * bsdfVal;
                     shadow = true;
-                    if (guide) neePending = true;
+                    // shadow blockers (pg_layout.h): the ray shadowRows would trace, (h.p, neeD, shadowTmin, the tmax
+                    // stored in sh_d.w below), tested against the listed triangles before anything is stored.  A
+                    // certain hit: no shadow ray; its contribution is dropped as shadowRows would drop it.
+                    if (!ENV && sc.num_blockers) {
+                        const float po[3] = {h.p.x, h.p.y, h.p.z}, pd[3] = {neeD.x, neeD.y, neeD.z};
+                        blocked = pg_ray_hits_blockers(sc.blk, sc.num_blockers, sc.absmax, po, pd,
+                                                       shadowTmin(f4(h.p, 0.0f)), neeDist * (1 - kShadowEpsilon));
+                        shadow = blocked == 0;
+                    }
+                    if (guide) neePending = shadow;  // a resolved ray's contribution is never used
                     else neeC = neeV * miWeight(emPdf, neeBp);
                 }
             }
@@ -911,7 +950,7 @@ __device__ __forceinline__ void shadeBlock(const GParams &g, const SceneDev &sc,
     if (base >= n) return;
     const uint32_t i = base + threadIdx.x;
     bool alive = false, shadow = false, probe = false;
-    uint32_t slot = 0, rkey = 0;
+    uint32_t slot = 0, rkey = 0, blocked = 0;
     if (i < n) slot = in.items[(size_t)s * in.stride + i];
     // the material table, staged in LDS once per block (the material read sits on the dependent chain
     // hit -> triangle -> material of every shaded vertex); larger tables stay in global memory
@@ -924,13 +963,25 @@ __device__ __forceinline__ void shadeBlock(const GParams &g, const SceneDev &sc,
     }
     if (i < n)
         shadeOne<MODEL, CAN_GUIDE, ENV>(g, sc, sd, p, slot, ldsMats ? reinterpret_cast<const GMat *>(smat) : sc.mats,
-                                        out.keys != nullptr, alive, shadow, probe, rkey);
+                                        out.keys != nullptr, alive, shadow, probe, rkey, blocked);
     if (out.keys)
         waveAppendKey(alive, slot, (uint16_t)rkey, out.items + (size_t)s * out.stride, out.keys + (size_t)s * out.stride,
                       out.counts + s);
     else
         waveAppend(alive, slot, out.items + (size_t)s * out.stride, out.counts + s);
     waveAppend(shadow, slot, shq.items + (size_t)s * shq.stride, shq.counts + s);
+    // shadow rays resolved against the blocker list: counted only (they stay in pg_stats.shadow_rays), and in the
+    // recording passes added to their blocker's count, as the any-hit rows would have
+    if (!ENV && sc.num_blockers) {
+        const unsigned long long m = __ballot(blocked != 0);
+        if (m) {
+            if ((threadIdx.x & 63) == 0) atomicAdd(shq.dropped + s, (uint32_t)__popcll(m));
+            if (sc.blk_counts && blockerRowCounted(bid / PG_QSHARDS)) {
+                waveKeyedAdd<uint32_t>(sc.blk_counts, blocked - 1u, 1u, blocked != 0);  // blocked: 1 + the triangle
+                if ((threadIdx.x & 63) == 0) atomicAdd(sc.blk_total, (uint32_t)__popcll(m));
+            }
+        }
+    }
     // doomed rays that miss every emitter box: the tracer's probe rows (never set with ENV or without the probe)
     if (!ENV && g.doom_probe) waveAppend(probe, slot, pq.items + (size_t)s * pq.stride, pq.counts + s);
     }
@@ -1051,27 +1102,31 @@ __global__ __launch_bounds__(256) void k_rsort_scatter(Queue q, uint32_t *hist, 
 // device atomics; a probe is also a segment and either a culled hit or an escape).
 template <bool ENV>
 __device__ __forceinline__ void tailShade(const GParams &g, const SceneDev &sc, const SDDev &sd, const PathDev &p,
-                                          uint32_t slot, uint32_t tri, bool &alive, bool &shadow, bool &probe) {
+                                          uint32_t slot, uint32_t tri, bool &alive, bool &shadow, bool &probe,
+                                          uint32_t &blocked) {
     uint32_t rk = 0;
     switch (sc.tclass[tri] & PG_TCLASS_MASK) {
-        case PG_CLASS_DIFFUSE: shadeOne<PG_BSDF_DIFFUSE, true, ENV>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, probe, rk); break;
+        case PG_CLASS_DIFFUSE: shadeOne<PG_BSDF_DIFFUSE, true, ENV>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, probe, rk, blocked); break;
         case PG_CLASS_ROUGHCONDUCTOR:
-            shadeOne<PG_BSDF_ROUGHCONDUCTOR, true, ENV>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, probe, rk);
+            shadeOne<PG_BSDF_ROUGHCONDUCTOR, true, ENV>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, probe, rk, blocked);
             break;
         case PG_CLASS_ROUGHDIELECTRIC:
-            shadeOne<PG_BSDF_ROUGHDIELECTRIC, true, ENV>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, probe, rk);
+            shadeOne<PG_BSDF_ROUGHDIELECTRIC, true, ENV>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, probe, rk, blocked);
             break;
-        case PG_CLASS_PLASTIC: shadeOne<PG_BSDF_PLASTIC, false, ENV>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, probe, rk); break;
+        case PG_CLASS_PLASTIC: shadeOne<PG_BSDF_PLASTIC, false, ENV>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, probe, rk, blocked); break;
         case PG_CLASS_ROUGHPLASTIC:
-            shadeOne<PG_BSDF_ROUGHPLASTIC, true, ENV>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, probe, rk);
+            shadeOne<PG_BSDF_ROUGHPLASTIC, true, ENV>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, probe, rk, blocked);
             break;
-        default: shadeOne<-1, false, ENV>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, probe, rk);
+        default: shadeOne<-1, false, ENV>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, probe, rk, blocked);
     }
 }
-template <bool ENV>
 #ifndef PG_TAIL_WAVES
 #define PG_TAIL_WAVES 0  // 0: the compiler's budget (A/B: 3)
 #endif
+// COUNT: the recording passes' instantiation (shadowRows).  On the sampled rows, one plain add per occluded ray to its
+// triangle's counter and one per shadow ray, occluded or not, to the single total: the one-address pattern that is too
+// slow for the bounce launches' rows, affordable here because the tail holds few paths
+template <bool ENV, bool COUNT = false>
 __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PG_TAIL_WAVES > 0 ? PG_TAIL_WAVES : 1))) void k_tail(GParams g, SceneDev sc, SDDev sd, PathDev p, Queue q,
                                                       unsigned long long *stats) {
     __shared__ uint32_t stack[2 * WIDE_LDS_STACK * TRACE_BLOCK];  // >= LDS_STACK words per thread
@@ -1080,17 +1135,32 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PG_
     const uint32_t s = blockIdx.x & (PG_QSHARDS - 1);
     const uint32_t rows = gridDim.x / PG_QSHARDS;  // grid capped at TRACE_MAX_BLOCKS: the overflow ring's size
     const uint32_t n = q.counts[s];
-    uint32_t segs = 0, esc = 0, shadows = 0, culled = 0, probes = 0;
+    uint32_t segs = 0, esc = 0, shadows = 0, culled = 0, probes = 0, drops = 0;
     for (uint32_t i = (blockIdx.x / PG_QSHARDS) * TRACE_BLOCK + threadIdx.x; i < n; i += rows * TRACE_BLOCK) {
         const uint32_t slot = q.items[(size_t)s * q.stride + i];
         uint32_t tri = __float_as_uint(ldS(&p.hit[slot]).y);
         while (tri != 0xFFFFFFFFu) {
             bool alive = false, shadow = false, probe = false;
-            tailShade<ENV>(g, sc, sd, p, slot, tri, alive, shadow, probe);
+            uint32_t blocked = 0;
+            tailShade<ENV>(g, sc, sd, p, slot, tri, alive, shadow, probe, blocked);
+            if (!ENV && blocked) {  // a shadow ray the blocker list resolved: counted, not traced
+                ++shadows;
+                ++drops;
+                if (COUNT && blockerRowCounted(i / TRACE_BLOCK)) {
+                    atomicAdd(sc.blk_counts + (blocked - 1u), 1u);
+                    atomicAdd(sc.blk_total, 1u);
+                }
+            }
             if (shadow) {  // shadowRows for this path
                 ++shadows;
                 const float4 o = ldS(&p.ray_o[slot]), d = ldS(&p.sh_d[slot]);
-                if (!occluded(sc, xyz(o), xyz(d), shadowTmin(o), d.w, wstk)) {
+                uint32_t btri;
+                const bool occ = occluded(sc, xyz(o), xyz(d), shadowTmin(o), d.w, wstk, btri);
+                if (COUNT && blockerRowCounted(i / TRACE_BLOCK)) {
+                    if (btri != 0xFFFFFFFFu) atomicAdd(sc.blk_counts + btri, 1u);
+                    atomicAdd(sc.blk_total, 1u);
+                }
+                if (!occ) {
                     const float4 c = ldS(&p.sh_c[slot]);
                     const float4 L = ldS(&p.rad[slot]);
                     stS(&p.rad[slot], make_float4(L.x + c.x, L.y + c.y, L.z + c.z, L.w));
@@ -1129,13 +1199,14 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PG_
         }
     }
     // wave-summed counters
-    unsigned long long a = segs, b = esc, c = shadows, e = culled, f = probes;
+    unsigned long long a = segs, b = esc, c = shadows, e = culled, f = probes, dr = drops;
     for (int off = 32; off > 0; off >>= 1) {
         a += __shfl_xor(a, off);
         b += __shfl_xor(b, off);
         c += __shfl_xor(c, off);
         e += __shfl_xor(e, off);
         f += __shfl_xor(f, off);
+        dr += __shfl_xor(dr, off);
     }
     if ((threadIdx.x & 63) == 0 && (a | b | c)) {
         atomicAdd(stats + 0, a);
@@ -1143,6 +1214,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PG_
         atomicAdd(stats + 2, c);
         if (e) atomicAdd(stats + 3, e);
         if (f) atomicAdd(stats + 4, f);
+        if (dr) atomicAdd(stats + 5, dr);
     }
 }
 
@@ -1595,6 +1667,16 @@ __global__ __launch_bounds__(TRACE_BLOCK) void k_trace_rays(SceneDev sc, const f
     h[3] = v;
 }
 
+// pg_blocker_test: the shader's blocker test on given rays (rows as k_trace_rays')
+__global__ __launch_bounds__(256) void k_blocker_test(SceneDev sc, const float *__restrict__ rays, uint32_t n,
+                                                      uint32_t *__restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *r = rays + 8 * (size_t)i;
+    const float o[3] = {r[0], r[1], r[2]}, d[3] = {r[4], r[5], r[6]};
+    out[i] = pg_ray_hits_blockers(sc.blk, sc.num_blockers, sc.absmax, o, d, r[3], r[7]) ? 1u : 0u;
+}
+
 __global__ __launch_bounds__(256) void k_bsdf_query(const GMat *mat, const float *wi, const float *u, const float *wog,
                                                     uint32_t n, float *out) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1734,23 +1816,28 @@ void pg_launch_shade_all(hipStream_t s, const GParams &g, const SceneDev &sc, co
     if (!total) return;
     hipLaunchKernelGGL(k_shade_all, dim3(total), dim3(SHADE_BLOCK), 0, s, g, sc, sd, p, cq, out, shq, pq, r);
 }
+// the recording passes count shadow blockers (sc.blk_counts is set only for them, never with an environment emitter)
+static inline bool blockersCounted(const GParams &g, const SceneDev &sc) { return g.record && sc.blk_counts && !sc.env; }
 void pg_launch_rays(hipStream_t s, const GParams &g, const SceneDev &sc, const PathDev &p, Queue q, uint32_t max_shard,
                     const Queue *class_queues, Queue shq, uint32_t max_shadow_shard, Queue pq) {
     ClassQueues cq;
     for (int c = 0; c < PG_CLASS_ROWS; ++c) cq.q[c] = class_queues[c];
     const uint32_t sb = max_shadow_shard ? shardGrid(max_shadow_shard, TRACE_BLOCK, TRACE_MAX_BLOCKS / PG_QSHARDS).x : 0;
+    const bool count = blockersCounted(g, sc);
     // the probe queue's shards are bounded as the shadow queue's (both hold vertices of the bounce just shaded)
     const uint32_t pb = (g.doom_probe && !sc.env) ? sb : 0;
     const uint32_t tb =
         max_shard ? shardGrid(max_shard, (PG_TRACE_PAIR ? 2 : 1) * TRACE_BLOCK, TRACE_MAX_BLOCKS / PG_QSHARDS).x : 0;
     if (sb + tb == 0) return;
     if (tb == 0) {  // no trace rows: k_rays needs at least one trace block per shard to stay sharded
-        hipLaunchKernelGGL(k_shadow, dim3(sb), dim3(TRACE_BLOCK), 0, s, sc, p, shq);
+        if (count) hipLaunchKernelGGL(k_shadow<true>, dim3(sb), dim3(TRACE_BLOCK), 0, s, sc, p, shq);
+        else hipLaunchKernelGGL(k_shadow<false>, dim3(sb), dim3(TRACE_BLOCK), 0, s, sc, p, shq);
         if (pb) hipLaunchKernelGGL(k_probe, dim3(pb), dim3(TRACE_BLOCK), 0, s, sc, p, pq, cq);
         return;
     }
     // sb + tb + pb <= 3 TRACE_MAX_BLOCKS: the overflow ring's size (pg_host.cpp ensurePaths)
     if (sc.env) hipLaunchKernelGGL(k_rays<true>, dim3(sb + tb + pb), dim3(TRACE_BLOCK), 0, s, g, sc, p, q, cq, shq, sb, pq, pb);
+    else if (count) hipLaunchKernelGGL((k_rays<false, true>), dim3(sb + tb + pb), dim3(TRACE_BLOCK), 0, s, g, sc, p, q, cq, shq, sb, pq, pb);
     else hipLaunchKernelGGL(k_rays<false>, dim3(sb + tb + pb), dim3(TRACE_BLOCK), 0, s, g, sc, p, q, cq, shq, sb, pq, pb);
 }
 void pg_launch_probe(hipStream_t s, const SceneDev &sc, const PathDev &p, Queue pq, uint32_t max_shard,
@@ -1761,10 +1848,11 @@ void pg_launch_probe(hipStream_t s, const SceneDev &sc, const PathDev &p, Queue 
     hipLaunchKernelGGL(k_probe, shardGrid(max_shard, TRACE_BLOCK, TRACE_MAX_BLOCKS / PG_QSHARDS), dim3(TRACE_BLOCK), 0, s,
                        sc, p, pq, cq);
 }
-void pg_launch_shadow(hipStream_t s, const SceneDev &sc, const PathDev &p, Queue q, uint32_t max_shard) {
+void pg_launch_shadow(hipStream_t s, const GParams &g, const SceneDev &sc, const PathDev &p, Queue q, uint32_t max_shard) {
     if (!max_shard) return;
-    hipLaunchKernelGGL(k_shadow, shardGrid(max_shard, TRACE_BLOCK, TRACE_MAX_BLOCKS / PG_QSHARDS), dim3(TRACE_BLOCK), 0,
-                       s, sc, p, q);
+    const dim3 grid = shardGrid(max_shard, TRACE_BLOCK, TRACE_MAX_BLOCKS / PG_QSHARDS);
+    if (blockersCounted(g, sc)) hipLaunchKernelGGL(k_shadow<true>, grid, dim3(TRACE_BLOCK), 0, s, sc, p, q);
+    else hipLaunchKernelGGL(k_shadow<false>, grid, dim3(TRACE_BLOCK), 0, s, sc, p, q);
 }
 void pg_launch_tail(hipStream_t s, const GParams &g, const SceneDev &sc, const SDDev &sd, const PathDev &p, Queue q,
                     uint32_t max_shard, unsigned long long *stats) {
@@ -1773,6 +1861,7 @@ void pg_launch_tail(hipStream_t s, const GParams &g, const SceneDev &sc, const S
     // ring (threadStack / threadWideStack, stride gridDim.x * TRACE_BLOCK) holds that many threads
     const dim3 grid = shardGrid(max_shard, TRACE_BLOCK, TRACE_MAX_BLOCKS / PG_QSHARDS);
     if (sc.env) hipLaunchKernelGGL(k_tail<true>, grid, dim3(TRACE_BLOCK), 0, s, g, sc, sd, p, q, stats);
+    else if (blockersCounted(g, sc)) hipLaunchKernelGGL((k_tail<false, true>), grid, dim3(TRACE_BLOCK), 0, s, g, sc, sd, p, q, stats);
     else hipLaunchKernelGGL(k_tail<false>, grid, dim3(TRACE_BLOCK), 0, s, g, sc, sd, p, q, stats);
 }
 template <uint32_t BINS>
@@ -1885,6 +1974,10 @@ void pg_launch_trace_rays(hipStream_t s, const SceneDev &sc, const float *rays, 
                           uint32_t *ovf) {
     if (!n) return;
     hipLaunchKernelGGL(k_trace_rays, dim3(blocks(n, TRACE_BLOCK)), dim3(TRACE_BLOCK), 0, s, sc, rays, n, any, hits, ovf);
+}
+void pg_launch_blocker_test(hipStream_t s, const SceneDev &sc, const float *rays, uint32_t n, uint32_t *out) {
+    if (!n) return;
+    hipLaunchKernelGGL(k_blocker_test, dim3(blocks(n, 256)), dim3(256), 0, s, sc, rays, n, out);
 }
 void pg_launch_bsdf_query(hipStream_t s, const GMat *mat, const float *wi, const float *u, const float *wog, uint32_t n,
                           float *out) {

@@ -385,6 +385,131 @@ inline uint32_t pg_emitter_boxes(const float *positions, const uint32_t *indices
     return n;
 }
 
+// Shadow blockers (SceneDev::blk): where next-event estimation almost always fails (an emitter behind a small
+// opening), nearly every shadow ray ends on one of a few large triangles.  The any-hit rows of the recording passes
+// count, per triangle, the shadow rays it blocked; after each recording pass the host lists up to PG_MAX_BLOCKERS
+// triangles that each blocked at least 1 / PG_BLOCKER_MIN_SHARE of all shadow rays of the recording passes, and
+// keeps the list only if together they blocked at least half of those rays (pg_select_blockers): where the light is
+// mostly visible the tests would cost every NEE vertex more than the few walks they save.  Then
+// shadeOne tests a new shadow ray against the listed TriAccel records before it stores anything: a certain hit drops
+// the ray (its stores, its queue entry and its any-hit walk), exactly as shadowRows would have dropped its
+// contribution.  The list only decides which rays are resolved early, never a result.
+//
+// "Certain" (pg_ray_hits_blockers): the shortcut may say "occluded" only where the 8-wide walk says it too.  The
+// walk's leaf test of the blocker is this test bit for bit (same record, o, d, tmin, tmax), so the walk accepts the
+// blocker if it reaches its leaf, i.e. if every ancestor slot passes max(tn_x, tn_y, tn_z, tmin) <= min(tf_x, tf_y,
+// tf_z, tmax) with tn_a = fma(q, 2^e idir_a, (p_a - o_a) idir_a) (pg_trace.h traverseWide; no padding).  The planes
+// X = p + q 2^e are rounded outward, so they enclose the triangle; q 2^e idir is exact, and the three roundings of
+// idir, (p - o) and their product displace a computed plane by at most d_pos = 2^-21 E along its axis, E = the
+// scene's largest |coordinate| + max |o_i| (an origin inside the scene: |p - o|, |X - o| <= E).  In t that is
+// d_pos / |d_a|.  The margins below make the exact hit point P clear every such displaced plane:
+//   - barycentrics u, v, 1 - u - v >= 2^-10.  TriAccel's own t carries at most 2^-22 E / |den| of cancellation
+//     (den = d.n / n_k), with |den| >= max|d| / 16 below that moves the point by <= 2^-18 E and, for a triangle whose
+//     box is at least E / 32 wide on both axes other than k (rec[11], set by the host: pg_blocker_record), its
+//     barycentrics by <= 2^-12: P's true weights are >= 2^-11, so P is at least 2^-11 W >= 2^-16 E inside the
+//     triangle's box on those two axes;
+//   - |d_k| >= max|d| / 16 (k = the record's projection axis, the one axis the box may be flat on).  A pair of slabs
+//     (a, b) stays ordered when one of them has slack >= d_pos (1 + |d_a| / |d_b|): with the flat axis as b that is
+//     17 d_pos = 2^-17 E on the other axis, half of what the barycentric margin leaves; the two wide axes cover
+//     each other with 2 d_pos;
+//   - t in [tmin + 2^-10 tmax, tmax - 2^-10 tmax] and tmax max|d| >= E / 32: the flat axis' planes sit at t -+
+//     (d_pos / |d_k| + the error of t) <= 1.5 * 2^-17 E / max|d| <= 2^-10 tmax / 2.6, inside [tmin, tmax].  (The shrink
+//     is absolute at both ends: tmin is only 1e-4 of the origin, so a shrink relative to tmin would be far less than a
+//     plane's rounding.)
+//   - every |d_a| > 1e-30: the walk replaces a zero component by +-1e-30 and picks near / far by d_a < 0, which
+//     for -0.0 disagree -- such a ray is left to the walk.
+// A ray that fails any margin is queued and walked as before.  The margins cost a negligible share of the culls.
+// Only every PG_BLOCKER_SAMPLE-th row (a block's share of a queue shard) is counted, with the number of shadow rays in those rows as
+// the total the shares refer to: a few triangles take nearly all the counts, and one add per wave and triangle on so
+// few addresses serialises in L2 (C3's training went from 70 to 112 ms with every row counted).  The selection needs
+// shares, not exact counts.  The counts are uint32 and cumulative over a job; once the total reaches 2^31 the host
+// stops counting and keeps the list it has (PG_BLOCKER_COUNT_STOP), so no counter wraps.  It also stops, with an empty
+// list, once PG_BLOCKER_DECIDE counted rays or more gave no list: such a scene pays for one or two small passes' counting.
+#define PG_MAX_BLOCKERS 8
+#define PG_BLOCKER_MIN_SHARE 64
+#define PG_BLOCKER_COUNT_STOP 0x80000000u
+#define PG_BLOCKER_SAMPLE 16u
+// counted shadow rays after which an empty selection is final for the job: each listed share is then known to about
+// 1 / sqrt(4096 / 64) of itself at the 1/64 threshold and the half-share bound to 1.6 %
+#define PG_BLOCKER_DECIDE 4096u
+#define PG_BLOCKER_MARGIN 9.765625e-4f  // 2^-10
+// blk: the listed records, 12 floats each: TriAccel rows 0-2 with [10] = bits(BVH-order id) and [11] = the smaller
+// width of the triangle's box on the two axes other than k.  absmax: the scene's largest |coordinate|.
+// Returns 1 + the id ([10]) of the first listed triangle that certainly blocks o + t d, t in [tmin, tmax]; 0: none.
+PG_HD inline uint32_t pg_ray_hits_blockers(const float (*blk)[12], uint32_t n, float absmax, const float o[3],
+                                           const float d[3], float tmin, float tmax) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const float E = absmax + fmaxf(fmaxf(fabsf(o[0]), fabsf(o[1])), fabsf(o[2]));
+    const float dmax = fmaxf(fmaxf(fabsf(d[0]), fabsf(d[1])), fabsf(d[2]));
+    const float dmin = fminf(fminf(fabsf(d[0]), fabsf(d[1])), fabsf(d[2]));
+    if (!(dmin > 1e-30f && tmax * dmax * 32.0f >= E)) return 0;
+    const float shrink = PG_BLOCKER_MARGIN * tmax;
+    for (uint32_t b = 0; b < n; ++b) {
+        const float *r = blk[b];
+        uint32_t k;
+        __builtin_memcpy(&k, r + 3, 4);
+        if (k > 2u || !(r[11] * 32.0f >= E)) continue;
+        // triHitRow0's arithmetic (pg_trace.h), in its order
+        const float ou = k == 0 ? o[1] : (k == 1 ? o[2] : o[0]), ov = k == 0 ? o[2] : (k == 1 ? o[0] : o[1]);
+        const float ok = k == 0 ? o[0] : (k == 1 ? o[1] : o[2]);
+        const float du = k == 0 ? d[1] : (k == 1 ? d[2] : d[0]), dv = k == 0 ? d[2] : (k == 1 ? d[0] : d[1]);
+        const float dk = k == 0 ? d[0] : (k == 1 ? d[1] : d[2]);
+        const float den = du * r[0] + dv * r[1] + dk;
+        if (!(fabsf(dk) * 16.0f >= dmax && fabsf(den) * 16.0f >= dmax)) continue;
+        const float tt = (r[2] - ou * r[0] - ov * r[1] - ok) / den;
+        if (!(tt >= tmin + shrink && tt <= tmax - shrink)) continue;
+        const float hu = ou + tt * du - r[4], hv = ov + tt * dv - r[5];
+        const float u = hv * r[6] + hu * r[7];
+        const float v = hu * r[8] + hv * r[9];
+        if (u >= PG_BLOCKER_MARGIN && v >= PG_BLOCKER_MARGIN && u + v <= 1.0f - PG_BLOCKER_MARGIN) {
+            uint32_t id;
+            __builtin_memcpy(&id, r + 10, 4);
+            return id + 1;  // ids are < 2^31
+        }
+    }
+    return 0;
+}
+// Host: the listed record of BVH-order triangle `id`: its TriAccel rows (3 float4), p0 / p1 / p2 its vertices
+inline void pg_blocker_record(const float *rows, const float *p0, const float *p1, const float *p2, uint32_t id,
+                              float *rec) {
+    __builtin_memcpy(rec, rows, 48);
+    uint32_t k;
+    __builtin_memcpy(&k, rows + 3, 4);
+    float w = __builtin_huge_valf();
+    for (uint32_t a = 0; a < 3; ++a) {
+        if (a == k) continue;
+        const float lo = fminf(fminf(p0[a], p1[a]), p2[a]), hi = fmaxf(fmaxf(p0[a], p1[a]), p2[a]);
+        w = fminf(w, hi - lo);
+    }
+    __builtin_memcpy(rec + 10, &id, 4);
+    rec[11] = k <= 2u ? w : 0.0f;
+}
+// Host: up to PG_MAX_BLOCKERS triangle ids by descending count, each with count * PG_BLOCKER_MIN_SHARE >= total, the
+// number of shadow rays (occluded or not) the counts were taken from: below that share eight tests per NEE vertex
+// cannot pay for themselves.  Equal counts go to the lower id, so the list is reproducible.  The list is empty
+// unless its triangles together blocked at least half of the total.  Returns the number written to ids.
+inline uint32_t pg_select_blockers(const uint32_t *counts, uint32_t n, uint64_t total, uint32_t *ids) {
+    uint32_t m = 0;
+    if (!total) return 0;
+    for (uint32_t t = 0; t < n; ++t) {
+        const uint32_t c = counts[t];
+        if (c == 0 || (uint64_t)c * PG_BLOCKER_MIN_SHARE < total) continue;
+        // insertion into the descending list; strict > keeps the lower id first among equals
+        uint32_t at = m;
+        while (at > 0 && c > counts[ids[at - 1]]) --at;
+        if (at >= PG_MAX_BLOCKERS) continue;
+        const uint32_t last = m < PG_MAX_BLOCKERS ? m : PG_MAX_BLOCKERS - 1;
+        for (uint32_t j = last; j > at; --j) ids[j] = ids[j - 1];
+        ids[at] = t;
+        if (m < PG_MAX_BLOCKERS) ++m;
+    }
+    uint64_t listed = 0;
+    for (uint32_t j = 0; j < m; ++j) listed += counts[ids[j]];
+    return 2 * listed >= total ? m : 0;
+}
+
 // Kernel-side constants of one render context.
 struct GParams {
     // camera

@@ -322,7 +322,10 @@ __device__ __forceinline__ bool traverseWide(const float4 *__restrict__ nodes, c
             float tt, bu, bv;
             if (triHitRow0(ra, tris, ta, o, d, tmin, tmax, tt, bu, bv) && acceptHit(tris, tt, tmax, ta, hitTri)) {
                 found = true;
-                if (ANY) return true;
+                if (ANY) {
+                    hitTri = ta;
+                    return true;
+                }
                 tmax = tt;
                 hitTri = ta;
                 hu = bu;
@@ -330,7 +333,10 @@ __device__ __forceinline__ bool traverseWide(const float4 *__restrict__ nodes, c
             }
             if (two && triHitRow0(rb, tris, tb, o, d, tmin, tmax, tt, bu, bv) && acceptHit(tris, tt, tmax, tb, hitTri)) {
                 found = true;
-                if (ANY) return true;
+                if (ANY) {
+                    hitTri = tb;
+                    return true;
+                }
                 tmax = tt;
                 hitTri = tb;
                 hu = bu;
@@ -347,7 +353,10 @@ __device__ __forceinline__ bool traverseWide(const float4 *__restrict__ nodes, c
             float tt, bu, bv;
             if (triHit(tris, tr, o, d, tmin, tmax, tt, bu, bv) && acceptHit(tris, tt, tmax, tr, hitTri)) {
                 found = true;
-                if (ANY) return true;
+                if (ANY) {
+                    hitTri = tr;
+                    return true;
+                }
                 tmax = tt;
                 hitTri = tr;
                 hu = bu;
@@ -919,14 +928,21 @@ __device__ __forceinline__ bool traverse(const float4 *__restrict__ nodes, const
 #ifndef PG_SHADOW4
 #define PG_SHADOW4 0
 #endif
-__device__ __forceinline__ bool occluded(const SceneDev &sc, f3 o, f3 d, float tmin, float tmax, const WStack &w) {
-    uint32_t tri = 0xFFFFFFFFu;
+// tri: the BVH-order triangle the 8-wide walk accepted (~0: no hit; PG_SHADOW4 builds do not report it)
+__device__ __forceinline__ bool occluded(const SceneDev &sc, f3 o, f3 d, float tmin, float tmax, const WStack &w,
+                                         uint32_t &tri) {
+    tri = 0xFFFFFFFFu;
     float u, v;
 #if PG_BVH4 && PG_SHADOW4
-    return traverse4<true>(sc.nodes, sc.tris, o, d, tmin, tmax, tri, u, v, TStack{w.lds, w.ovf, w.ostride});
+    uint32_t t4 = 0xFFFFFFFFu;
+    return traverse4<true>(sc.nodes, sc.tris, o, d, tmin, tmax, t4, u, v, TStack{w.lds, w.ovf, w.ostride});
 #else
     return traverseWide<true>(sc.wnodes, sc.wtris, o, d, tmin, tmax, tri, u, v, w);
 #endif
+}
+__device__ __forceinline__ bool occluded(const SceneDev &sc, f3 o, f3 d, float tmin, float tmax, const WStack &w) {
+    uint32_t tri;
+    return occluded(sc, o, d, tmin, tmax, w, tri);
 }
 
 __device__ __forceinline__ float miWeight(float a, float b) {

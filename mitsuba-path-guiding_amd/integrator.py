@@ -288,6 +288,24 @@ class Device:
         out["culled"] = n.value  # segments whose doomed vertex the tracer culled (pg_capi.h pg_get_culled)
         self._chk(self.lib.pg_get_probes(self.h, C.byref(n)))
         out["probes"] = n.value  # segments answered by an any-hit probe (pg_capi.h pg_get_probes)
+        self._chk(self.lib.pg_get_shadow_culled(self.h, C.byref(n)))
+        out["shadow_culled"] = n.value  # shadow rays resolved against the blocker list (pg_get_shadow_culled)
+        return out
+
+    def blockers(self):
+        """The current shadow-blocker list (pg_get_blockers), most frequent first: (BVH-order triangle ids, the same
+        triangles' indices in the uploaded scene)."""
+        ids, orig = np.zeros(8, np.uint32), np.zeros(8, np.uint32)
+        n = C.c_uint32()
+        self._chk(self.lib.pg_get_blockers(self.h, _p(ids), _p(orig), C.byref(n)))
+        return ids[: n.value].copy(), orig[: n.value].copy()
+
+    def blocker_test(self, rays, tri_ids):
+        """pg_blocker_test: the shader's blocker test on rays (n x 8) against the BVH-order triangles tri_ids."""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        ids = np.ascontiguousarray(tri_ids, np.uint32)
+        out = np.zeros(len(rays), np.uint32)
+        self._chk(self.lib.pg_blocker_test(self.h, _p(rays), len(rays), _p(ids), len(ids), _p(out)))
         return out
 
     def local_pixel_count(self):
