@@ -388,6 +388,70 @@ pg_status pg_rfilter_table(int32_t type, float param, float *radius_out, float *
  * PG_ERR_STATE when no filter is set.  pg_reset_film clears it; pg_comm_reduce_film sums it (int64, exact). */
 pg_status pg_set_rfilter(void *ctx, float radius, const float *values /* [32] or NULL */);
 pg_status pg_read_film_filtered(void *ctx, float *rgbw, int64_t *raw);
+/* ---- textures: a bitmap or a checkerboard as the diffuse reflectance of a material ------------------------------
+ * New entry points; pg_config, pg_stats, pg_scene_desc, pg_material and PG_ABI_VERSION are unchanged.  While no
+ * texture is bound, no texture buffer is allocated on the device, no kernel compiled for textures is launched and
+ * every result is bit for bit what it was.  (What the feature costs every scene -- one more, empty, material-class
+ * queue per lane, a ninth counter row per bounce and host copies of the triangle indices, material records and
+ * triangle classes -- is listed in DESIGN.md section 3.)
+ *
+ * Only the lookup without ray differentials (Texture2D::eval(its, false), texture.cpp:112-121): the path integrator
+ * has no uv partials after the first vertex, and for filterType nearest / bilinear the reference uses none at all.
+ *   uv   = t0 * b.x + t1 * b.y + t2 * b.z, b = (1 - u - v, u, v) the hit's barycentrics (skdtree.h:355,398-405;
+ *          float32, no contraction); without texcoords uv = (u, v)
+ *   uv'  = (uv.x * uscale, uv.y * vscale) + (uoffset, voffset)
+ *   PG_TEXTURE_BITMAP (bitmap.cpp:431-449, MIP level 0, mipmap.h:503-596), float32 RGB texels, texel (x, y) at
+ *          rgb[3 * (y * width + x)]; a non-finite uv' gives 0.
+ *          PG_TEXFILTER_NEAREST: texel(floor(u' W), floor(v' H)).
+ *          PG_TEXFILTER_BILINEAR: u = u' W - 0.5, x = floor(u), dx1 = u - x, dx2 = 1 - dx1 (y alike):
+ *          T(x, y) dx2 dy2 + T(x, y + 1) dx2 dy1 + T(x + 1, y) dx1 dy2 + T(x + 1, y + 1) dx1 dy1, summed left to right.
+ *          texel() wraps x, then y (PG_TEXWRAP_*): repeat (positive modulo), clamp, mirror (x mod 2 W, then
+ *          2 W - x - 1 when x >= W), zero, one.
+ *   PG_TEXTURE_CHECKERBOARD (checkerboard.cpp:66-74): x = 2 mod((int)(u' 2), 2) - 1 (the conversion truncates toward
+ *          zero), y alike; color0 where x y == 1, else color1.
+ * The texel address is clamped into the image for every finite uv'; beyond |u' W| = 2^30 the colour is unspecified.
+ * The looked-up value replaces diffuse.reflectance / plastic.diffuseReflectance / roughplastic.diffuseReflectance at
+ * every vertex (BSDF value, sampling weight, albedo, the guide-fraction bound and the first-hit albedo of the
+ * denoiser buffers).  plastic / roughplastic take their specular sampling weight from the texture's average
+ * (Texture::getAverage, plastic.cpp:201-202): `average`, or where average[0] < 0 the mean of the texels / (color0 +
+ * color1) / 2.  Deviations from the reference: filterType ewa and trilinear are to be passed as bilinear (the
+ * reference filters camera-ray hits with the ray differentials; every later vertex is level-0 bilinear there too),
+ * and the shading frame keeps dpdu = p1 - p0 (no computeUVTangents). */
+enum { PG_TEXTURE_BITMAP = 0, PG_TEXTURE_CHECKERBOARD = 1 };
+enum { PG_TEXFILTER_NEAREST = 0, PG_TEXFILTER_BILINEAR = 1 };
+enum { PG_TEXWRAP_REPEAT = 0, PG_TEXWRAP_CLAMP = 1, PG_TEXWRAP_MIRROR = 2, PG_TEXWRAP_ZERO = 3, PG_TEXWRAP_ONE = 4 };
+typedef struct pg_texture {
+    uint32_t type;         /* PG_TEXTURE_* */
+    uint32_t width;        /* bitmap only */
+    uint32_t height;
+    uint32_t filter;       /* PG_TEXFILTER_* */
+    const float *rgb;      /* width * height * 3, finite and >= 0; copied by pg_set_textures */
+    uint32_t wrap_u;       /* PG_TEXWRAP_* */
+    uint32_t wrap_v;
+    float uscale, vscale;
+    float uoffset, voffset;
+    float color0[3];       /* checkerboard only */
+    float color1[3];
+    float average[3];      /* Texture::getAverage; average[0] < 0: computed here */
+    uint32_t pad0;
+} pg_texture;
+typedef struct pg_texture_binding {
+    uint32_t material;     /* its diffuse reflectance is the slot: diffuse, plastic or roughplastic */
+    uint32_t texture;
+} pg_texture_binding;
+/* texcoords: 2 * num_vertices floats of the uploaded scene, or NULL (uv = the barycentrics).  After pg_upload_scene
+ * and before the first render pass of that scene (PG_ERR_STATE otherwise); a later pg_upload_scene clears the
+ * textures; n_bindings == 0 turns them off.  PG_ERR_INVALID: a zero-sized bitmap, a non-finite or negative texel or
+ * colour, a non-finite scale or offset, an enum or index out of range, a material without a diffuse slot, a material
+ * bound twice, the volumetric integrator. */
+pg_status pg_set_textures(void *ctx, const pg_texture *textures, uint32_t n_textures,
+                          const pg_texture_binding *bindings, uint32_t n_bindings, const float *texcoords);
+/* Unit entry points (parity tests).  pg_texture_query: the device lookup of `texture` (not necessarily bound; needs
+ * only a context) at n raw uv pairs, the uv transform included; out: n x 3.  pg_hit_uvs: the closest hit's
+ * interpolated uv before any texture's transform (rays: n x 8 as pg_trace_rays; out: n x 2, (0, 0) for a miss), with
+ * the texcoords of the last pg_set_textures, else the barycentrics. */
+pg_status pg_texture_query(void *ctx, const pg_texture *texture, const float *uv, uint64_t n, float *out);
+pg_status pg_hit_uvs(void *ctx, const float *rays, uint64_t n, float *out);
 pg_status pg_get_stats(void *ctx, pg_stats *stats);
 /* Path integrator: segments (counted in pg_stats.segments, not in escaped) whose hit was culled by the
  * closest-hit kernels since create: the ray's next vertex had already lost its Russian roulette, or was past the

@@ -21,6 +21,9 @@ MAJORANT_CELL = 16  # voxels per majorant-grid cell edge (pg_layout.h PG_MAJORAN
 PG_DIST_BECKMANN, PG_DIST_GGX = 0, 1
 PG_MAT_TWOSIDED, PG_MAT_NONLINEAR, PG_MAT_SAMPLE_ALL = 1, 2, 4
 PG_RFILTER_BOX, PG_RFILTER_TENT, PG_RFILTER_GAUSSIAN = 0, 1, 2
+PG_TEXTURE_BITMAP, PG_TEXTURE_CHECKERBOARD = 0, 1
+PG_TEXFILTER_NEAREST, PG_TEXFILTER_BILINEAR = 0, 1
+PG_TEXWRAP_REPEAT, PG_TEXWRAP_CLAMP, PG_TEXWRAP_MIRROR, PG_TEXWRAP_ZERO, PG_TEXWRAP_ONE = range(5)
 
 # EBSDFType bits (include/mitsuba/render/bsdf.h:224-262)
 ENull, EDiffuseReflection, EDiffuseTransmission, EGlossyReflection = 0x1, 0x2, 0x4, 0x8
@@ -60,6 +63,17 @@ class pg_emitter(C.Structure):
 class pg_envmap(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("rgb", C.POINTER(C.c_float)),
                 ("to_world", C.c_float * 9), ("scale", C.c_float), ("pad0", C.c_uint32), ("pad1", C.c_uint32)]
+
+
+class pg_texture(C.Structure):
+    _fields_ = [("type", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("filter", C.c_uint32),
+                ("rgb", C.POINTER(C.c_float)), ("wrap_u", C.c_uint32), ("wrap_v", C.c_uint32),
+                ("uscale", C.c_float), ("vscale", C.c_float), ("uoffset", C.c_float), ("voffset", C.c_float),
+                ("color0", C.c_float * 3), ("color1", C.c_float * 3), ("average", C.c_float * 3), ("pad0", C.c_uint32)]
+
+
+class pg_texture_binding(C.Structure):
+    _fields_ = [("material", C.c_uint32), ("texture", C.c_uint32)]
 
 
 class pg_camera(C.Structure):
@@ -176,6 +190,9 @@ SIGNATURES = [
     ("pg_rfilter_table", C.c_int32, [C.c_int32, C.c_float, C.POINTER(C.c_float), VP]),
     ("pg_set_rfilter", C.c_int32, [VP, C.c_float, VP]),
     ("pg_read_film_filtered", C.c_int32, [VP, VP, VP]),
+    ("pg_set_textures", C.c_int32, [VP, C.POINTER(pg_texture), C.c_uint32, C.POINTER(pg_texture_binding), C.c_uint32, VP]),
+    ("pg_texture_query", C.c_int32, [VP, C.POINTER(pg_texture), VP, C.c_uint64, VP]),
+    ("pg_hit_uvs", C.c_int32, [VP, VP, C.c_uint64, VP]),
     ("pg_get_stats", C.c_int32, [VP, C.POINTER(pg_stats)]),
     ("pg_get_culled", C.c_int32, [VP, C.POINTER(C.c_uint64)]),
     ("pg_get_probes", C.c_int32, [VP, C.POINTER(C.c_uint64)]),

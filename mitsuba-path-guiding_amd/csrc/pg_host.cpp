@@ -29,10 +29,10 @@ namespace {
 constexpr uint32_t kStackDepth = 48;  // must match STACK_DEPTH in pg_kernels.hip
 constexpr uint32_t kMaxBounces = 1100;     // > gpu_depth_cap default (1024) + 2
 // per-bounce device counters (words): [0, 64) shard counts of the live queue entering the bounce,
-// [64, 128) shadow-queue shard counts, [128, 640) shard counts of the PG_NUM_CLASSES material-class
-// queues followed by the escaped-ray and the culled-hit counts (PG_CLASS_ROWS rows), [640, 704) shard counts of the
-// probe queue the bounce's shading fills (pg_layout.h "Doom probe")
-constexpr uint32_t kBounceWords = 768;
+// [64, 128) shadow-queue shard counts, [128, 704) shard counts of the PG_NUM_CLASSES material-class
+// queues followed by the escaped-ray and the culled-hit counts (PG_CLASS_ROWS rows), [704, 768) shard counts of the
+// probe queue the bounce's shading fills (pg_layout.h "Doom probe"), [768, 832) the dropped shadow rays
+constexpr uint32_t kBounceWords = 832;
 constexpr uint32_t kShadowCounts = PG_QSHARDS, kClassCounts = 2 * PG_QSHARDS;
 constexpr uint32_t kProbeCounts = kClassCounts + PG_CLASS_ROWS * PG_QSHARDS;
 // shadow rays the shader resolved against the blocker list (Queue::dropped of the shadow queue)
@@ -230,6 +230,15 @@ struct Ctx {
     float blk[PG_MAX_BLOCKERS][12] = {};
     float absmax = 0.0f;  // the scene's largest |coordinate|
     std::vector<GMat> host_mats;
+    // textures (pg_set_textures): nothing is allocated while `textured` is false.  base_mats / base_tclass: the
+    // untextured scene's material records and triangle classes, put back when the textures are turned off
+    bool textured = false;
+    bool scene_rendered = false;  // a render pass ran on the uploaded scene: its textures can no longer change
+    DevBuf tuv, tex, mtex, texels;
+    std::vector<GMat> base_mats;
+    std::vector<uint8_t> base_tclass;
+    std::vector<uint32_t> host_indices;  // the uploaded scene's triangles (their vertices' texcoords)
+    uint32_t num_vertices = 0;
     float scene_lo[3] = {0, 0, 0}, scene_hi[3] = {0, 0, 0};
     // shard
     std::vector<uint32_t> local_pixels;
@@ -435,6 +444,11 @@ SceneDev sceneView(const Ctx *c) {
     sc.absmax = c->absmax;
     sc.blk_counts = sc.blk_total = nullptr;  // set by the recording passes
     std::memcpy(sc.blk, c->blk, sizeof(sc.blk));
+    if (c->textured) {
+        sc.tuv = c->tuv.as<float4>();
+        sc.tex = c->tex.as<GTex>();
+        sc.mtex = c->mtex.as<uint32_t>();
+    }
     return sc;
 }
 
@@ -1011,6 +1025,241 @@ pg_status pg_set_rfilter(void *ctx, float radius, const float *values) {
     return c->has_scene ? setupFiltered(c) : PG_OK;
 }
 
+// ---- textures (pg_capi.h pg_set_textures) ---------------------------------------------------------------------------
+namespace {
+// pg_texture -> GTex (texels left null) with its validation; err: what is wrong with it
+bool makeGTex(const pg_texture &t, GTex &g, std::string &err) {
+    g = GTex{};
+    if (t.type > PG_TEXTURE_CHECKERBOARD) return err = "unknown texture type", false;
+    if (t.filter > PG_TEXFILTER_BILINEAR) return err = "unknown filter", false;
+    if (t.wrap_u > PG_TEXWRAP_ONE || t.wrap_v > PG_TEXWRAP_ONE) return err = "unknown wrap mode", false;
+    for (float x : {t.uscale, t.vscale, t.uoffset, t.voffset})
+        if (!std::isfinite(x)) return err = "non-finite uv scale or offset", false;
+    if (t.type == PG_TEXTURE_BITMAP) {
+        if (t.width == 0 || t.height == 0) return err = "zero-sized bitmap", false;
+        if (t.width > (1u << 24) || t.height > (1u << 24) || (uint64_t)t.width * t.height > (1ull << 28))
+            return err = "bitmap too large", false;
+        if (!t.rgb) return err = "bitmap without texels", false;
+        for (size_t i = 0; i < (size_t)3 * t.width * t.height; ++i)
+            if (!std::isfinite(t.rgb[i]) || t.rgb[i] < 0) return err = "non-finite or negative texel", false;
+        g.width = t.width;
+        g.height = t.height;
+    } else {
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(t.color0[k]) || t.color0[k] < 0 || !std::isfinite(t.color1[k]) || t.color1[k] < 0)
+                return err = "non-finite or negative checkerboard colour", false;
+    }
+    g.mode = t.type | (t.filter << 4) | (t.wrap_u << 8) | (t.wrap_v << 12);
+    g.uscale = t.uscale;
+    g.vscale = t.vscale;
+    g.uoffset = t.uoffset;
+    g.voffset = t.voffset;
+    for (int k = 0; k < 3; ++k) {
+        g.color0[k] = t.color0[k];
+        g.color1[k] = t.color1[k];
+    }
+    return true;
+}
+// float4 texels of a bitmap
+void texelRows(const pg_texture &t, std::vector<float> &o) {
+    o.assign((size_t)4 * t.width * t.height, 0.0f);
+    for (size_t i = 0; i < (size_t)t.width * t.height; ++i)
+        for (int k = 0; k < 3; ++k) o[4 * i + k] = t.rgb[3 * i + k];
+}
+// Texture::getAverage (the caller's, or the mean of the level-0 texels / of the two colours) and the per-channel
+// maximum of the texture's values
+void texAverageMax(const pg_texture &t, float avg[3], float mx[3]) {
+    for (int k = 0; k < 3; ++k) {
+        if (t.type == PG_TEXTURE_CHECKERBOARD) {
+            avg[k] = (t.color0[k] + t.color1[k]) * 0.5f;
+            mx[k] = std::max(t.color0[k], t.color1[k]);
+        } else {
+            double sum = 0;
+            mx[k] = 0.0f;
+            const size_t n = (size_t)t.width * t.height;
+            for (size_t i = 0; i < n; ++i) {
+                sum += t.rgb[3 * i + k];
+                mx[k] = std::max(mx[k], t.rgb[3 * i + k]);
+            }
+            avg[k] = (float)(sum / (double)n);
+        }
+        // zero / one wrap modes add their constant to the range
+        if (t.type == PG_TEXTURE_BITMAP && (t.wrap_u == PG_TEXWRAP_ONE || t.wrap_v == PG_TEXWRAP_ONE)) mx[k] = std::max(mx[k], 1.0f);
+    }
+    if (!(t.average[0] < 0))
+        for (int k = 0; k < 3; ++k) avg[k] = t.average[k];
+}
+// the untextured scene's materials and triangle classes back on the device
+pg_status clearTextures(Ctx *c) {
+    if (!c->textured) return PG_OK;
+    c->textured = false;
+    c->host_mats = c->base_mats;
+    pg_status s;
+    if ((s = upload(c, c->mats, c->host_mats)) || (s = upload(c, c->tclass, c->base_tclass))) return s;
+    HIPC(c, hipStreamSynchronize(c->stream));
+    for (DevBuf *b : {&c->tuv, &c->tex, &c->mtex, &c->texels}) b->release();
+    return PG_OK;
+}
+}  // namespace
+
+pg_status pg_set_textures(void *ctx, const pg_texture *textures, uint32_t n_textures, const pg_texture_binding *bindings,
+                          uint32_t n_bindings, const float *texcoords) {
+    Ctx *c = (Ctx *)ctx;
+    if (!c) return fail(nullptr, PG_ERR_INVALID, "pg_set_textures: null context");
+    if (c->cfg.integrator != PG_INTEGRATOR_PATH)
+        return fail(c, PG_ERR_INVALID, "pg_set_textures: the volumetric integrator does not support textures");
+    if (!c->has_scene) return fail(c, PG_ERR_STATE, "pg_set_textures: no scene uploaded");
+    if (c->scene_rendered) return fail(c, PG_ERR_STATE, "pg_set_textures: a render pass has already run on this scene");
+    if ((n_textures && !textures) || (n_bindings && !bindings)) return fail(c, PG_ERR_INVALID, "pg_set_textures: null argument");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    // validate everything before anything changes
+    std::vector<GTex> gtex(n_textures);
+    for (uint32_t i = 0; i < n_textures; ++i) {
+        std::string err;
+        if (!makeGTex(textures[i], gtex[i], err))
+            return fail(c, PG_ERR_INVALID, "pg_set_textures: texture " + std::to_string(i) + ": " + err);
+        if (!(textures[i].average[0] < 0))
+            for (int k = 0; k < 3; ++k)
+                if (!std::isfinite(textures[i].average[k]) || textures[i].average[k] < 0)
+                    return fail(c, PG_ERR_INVALID, "pg_set_textures: texture " + std::to_string(i) + ": bad average");
+    }
+    std::vector<uint32_t> mtex(c->num_mats, 0xFFFFFFFFu);
+    for (uint32_t b = 0; b < n_bindings; ++b) {
+        const pg_texture_binding &tb = bindings[b];
+        if (tb.material >= c->num_mats || tb.texture >= n_textures)
+            return fail(c, PG_ERR_INVALID, "pg_set_textures: binding " + std::to_string(b) + ": index out of range");
+        const uint32_t model = c->base_mats[tb.material].model;
+        if (model != PG_BSDF_DIFFUSE && model != PG_BSDF_PLASTIC && model != PG_BSDF_ROUGHPLASTIC)
+            return fail(c, PG_ERR_INVALID, "pg_set_textures: binding " + std::to_string(b) +
+                                               ": the material's model has no diffuse reflectance");
+        if (mtex[tb.material] != 0xFFFFFFFFu)
+            return fail(c, PG_ERR_INVALID, "pg_set_textures: material " + std::to_string(tb.material) + " is bound twice");
+        mtex[tb.material] = tb.texture;
+    }
+    if (texcoords)
+        for (size_t i = 0; i < (size_t)2 * c->num_vertices; ++i)
+            if (!std::isfinite(texcoords[i])) return fail(c, PG_ERR_INVALID, "pg_set_textures: non-finite texcoord");
+    if (pg_status s = clearTextures(c)) return s;
+    if (n_bindings == 0) return PG_OK;
+
+    // texels: one buffer, each bitmap 256-B aligned
+    std::vector<float> texels;
+    std::vector<size_t> at(n_textures, 0);
+    for (uint32_t i = 0; i < n_textures; ++i) {
+        if (textures[i].type != PG_TEXTURE_BITMAP) continue;
+        texels.resize((texels.size() + 63) & ~(size_t)63, 0.0f);
+        at[i] = texels.size();
+        std::vector<float> rows;
+        texelRows(textures[i], rows);
+        texels.insert(texels.end(), rows.begin(), rows.end());
+    }
+    // from here on a failure puts the untextured scene back (restoreBase): the context never holds half a texture set
+    auto restoreBase = [&](pg_status why) {
+        const std::string msg = c->err;
+        c->textured = true;  // so that clearTextures re-uploads the base records and classes
+        (void)clearTextures(c);
+        c->err = msg;
+        return why;
+    };
+    pg_status s;
+    if ((s = upload(c, c->texels, texels))) return restoreBase(s);
+    for (uint32_t i = 0; i < n_textures; ++i)
+        if (textures[i].type == PG_TEXTURE_BITMAP) gtex[i].texels = c->texels.as<float>() + at[i];
+    // the bound materials: specWeight from the texture's average (plastic.cpp:201-202, roughplastic.cpp:258-262) and
+    // wbound from its per-channel maximum, an upper bound only (shadeOne computes the vertex's own)
+    std::vector<GMat> mats = c->base_mats;
+    for (uint32_t m = 0; m < c->num_mats; ++m) {
+        if (mtex[m] == 0xFFFFFFFFu) continue;
+        GMat &gm = mats[m];
+        float avg[3], mx[3];
+        texAverageMax(textures[mtex[m]], avg, mx);
+        if (gm.model != PG_BSDF_DIFFUSE) {
+            const float dAvg = luminance(avg), sAvg = luminance(gm.spec);
+            gm.specWeight = sAvg / (dAvg + sAvg);
+        }
+        float a[3];
+        for (int k = 0; k < 3; ++k) a[k] = gm.model == PG_BSDF_DIFFUSE ? mx[k] : mx[k] * 0.5f + gm.spec[k] * 0.5f;
+        gm.wbound = std::max(std::max(a[0], a[1]), a[2]);
+    }
+    // per BVH-order triangle: the vertices' texcoords (pg_layout.h PG_TRI_UV_F4), and the textured class
+    const uint32_t nt = c->num_tris;
+    std::vector<float> tuv((size_t)4 * PG_TRI_UV_F4 * nt, 0.0f);
+    std::vector<uint8_t> tclass = c->base_tclass;
+    for (uint32_t k = 0; k < nt; ++k) {
+        const float *rec = &c->host_shade[4 * PG_TRI_SHADE_STRIDE * (size_t)k];
+        uint32_t bits, orig;
+        std::memcpy(&bits, rec + 3, 4);
+        std::memcpy(&orig, rec + 11, 4);
+        float *o = &tuv[(size_t)4 * PG_TRI_UV_F4 * k];
+        if (texcoords) {
+            for (int v = 0; v < 3; ++v) {
+                const uint32_t vi = c->host_indices[3 * (size_t)orig + v];
+                o[2 * v] = texcoords[2 * (size_t)vi];
+                o[2 * v + 1] = texcoords[2 * (size_t)vi + 1];
+            }
+        } else {  // Intersection::uv without texcoords: (b.y, b.z)
+            o[2] = 1.0f;
+            o[5] = 1.0f;
+        }
+        if (mtex[bits & 0xFFFFu] != 0xFFFFFFFFu) tclass[k] = (uint8_t)(PG_CLASS_TEXTURED | (tclass[k] & PG_TCLASS_EMITTER));
+    }
+    if ((s = upload(c, c->tuv, tuv)) || (s = upload(c, c->tex, gtex)) || (s = upload(c, c->mtex, mtex)) ||
+        (s = upload(c, c->mats, mats)) || (s = upload(c, c->tclass, tclass)))
+        return restoreBase(s);
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return restoreBase(fail(c, PG_ERR_HIP, "pg_set_textures: upload failed"));
+    c->host_mats = mats;
+    c->textured = true;
+    return PG_OK;
+}
+
+pg_status pg_texture_query(void *ctx, const pg_texture *texture, const float *uv, uint64_t n, float *out) {
+    Ctx *c = (Ctx *)ctx;
+    if (!c || !texture || (!uv && n) || (!out && n)) return fail(c, PG_ERR_INVALID, "pg_texture_query: null argument");
+    if (n > 0xFFFFFFFFull / 3) return fail(c, PG_ERR_INVALID, "pg_texture_query: too many points");
+    GTex g;
+    std::string err;
+    if (!makeGTex(*texture, g, err)) return fail(c, PG_ERR_INVALID, "pg_texture_query: " + err);
+    HIPC(c, hipSetDevice(c->cfg.device));
+    if (!n) return PG_OK;
+    DevBuf dt, dg, du, dout;
+    if (texture->type == PG_TEXTURE_BITMAP) {
+        std::vector<float> rows;
+        texelRows(*texture, rows);
+        HIPC(c, dt.alloc(rows.size() * 4));
+        HIPC(c, hipMemcpy(dt.p, rows.data(), rows.size() * 4, hipMemcpyHostToDevice));
+        g.texels = dt.as<float>();
+    }
+    HIPC(c, dg.alloc(sizeof(GTex)));
+    HIPC(c, du.alloc(n * 8));
+    HIPC(c, dout.alloc(n * 12));
+    HIPC(c, hipMemcpy(dg.p, &g, sizeof(GTex), hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpyAsync(du.p, uv, n * 8, hipMemcpyHostToDevice, c->stream));
+    pg_launch_texture_query(c->stream, dg.as<GTex>(), du.as<float>(), (uint32_t)n, dout.as<float>());
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipMemcpyAsync(out, dout.p, n * 12, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    return PG_OK;
+}
+
+pg_status pg_hit_uvs(void *ctx, const float *rays, uint64_t n, float *out) {
+    Ctx *c = (Ctx *)ctx;
+    if (!c || (!rays && n) || (!out && n)) return fail(c, PG_ERR_INVALID, "pg_hit_uvs: null argument");
+    if (!c->has_scene) return fail(c, PG_ERR_STATE, "pg_hit_uvs: no scene");
+    if (n > 0xFFFFFFFFull) return fail(c, PG_ERR_INVALID, "pg_hit_uvs: too many rays");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    if (!n) return PG_OK;
+    DevBuf r, o, ovf;
+    HIPC(c, r.alloc(n * 32));
+    HIPC(c, o.alloc(n * 8));
+    HIPC(c, ovf.alloc(pg_stack_overflow_words(pg_trace_rays_threads(n)) * 4));
+    HIPC(c, hipMemcpyAsync(r.p, rays, n * 32, hipMemcpyHostToDevice, c->stream));
+    pg_launch_hit_uvs(c->stream, sceneView(c), r.as<float>(), (uint32_t)n, o.as<float>(), ovf.as<uint32_t>());
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipMemcpyAsync(out, o.p, n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    return PG_OK;
+}
+
 pg_status pg_read_film_filtered(void *ctx, float *rgbw, int64_t *raw) {
     Ctx *c = (Ctx *)ctx;
     if (!c) return fail(nullptr, PG_ERR_INVALID, "pg_read_film_filtered: null context");
@@ -1171,6 +1420,13 @@ pg_status pg_upload_scene(void *ctx, const pg_scene_desc *d) {
     HIPC(c, hipMemsetAsync(c->blk_counts.p, 0, ((size_t)nt + 1) * 4, c->stream));
     c->host_tris = bvh.tris;
     c->host_shade = shade;
+    // a new scene has no textures (pg_set_textures)
+    c->textured = false;
+    c->scene_rendered = false;
+    for (DevBuf *b : {&c->tuv, &c->tex, &c->mtex, &c->texels}) b->release();
+    c->base_tclass = tclass;
+    c->host_indices.assign(d->indices, d->indices + 3 * (size_t)nt);
+    c->num_vertices = d->num_vertices;
     c->host_mats.clear();
     for (uint32_t m = 0; m < d->num_materials; ++m) c->host_mats.push_back(makeGMat(d->materials[m]));
     // roughplastic: rough-transmittance slice + internal diffuse Fresnel per material
@@ -1195,6 +1451,7 @@ pg_status pg_upload_scene(void *ctx, const pg_scene_desc *d) {
     pg_status s;
     if ((s = upload(c, c->rtab, rtab))) return s;
     for (auto &mo : rtabOf) c->host_mats[mo.first].rtrans = c->rtab.as<float>() + mo.second;
+    c->base_mats = c->host_mats;
     c->bvh_top_nodes = std::min<uint32_t>(bvh.top_nodes, PG_BVH4 ? PG_BVH4_TOP_NODES : PG_BVH_TOP_NODES);
     if ((s = upload(c, c->nodes, bvh.nodes)) || (s = upload(c, c->tris, bvh.tris)) ||
         (s = upload(c, c->wnodes, bvh.wnodes)) || (s = upload(c, c->tshade, shade)) ||
@@ -1931,6 +2188,7 @@ pg_status pg_render_pass(void *ctx, uint32_t spp, uint32_t sample_offset, int32_
 
 static pg_status renderPass(Ctx *c, uint32_t spp, uint32_t sample_offset, int32_t record) {
     const uint32_t npix = (uint32_t)c->local_pixels.size();
+    c->scene_rendered = true;
     if (npix == 0 || spp == 0) return PG_OK;
     if (c->cfg.integrator == PG_INTEGRATOR_VOLPATH) return renderVolpath(c, spp, sample_offset, record && c->cfg.guiding);
     const bool rec = record && c->cfg.guiding;

@@ -29,6 +29,10 @@ struct SceneDev {
     uint32_t *blk_counts;   // per BVH-order triangle: shadow rays it blocked (recording passes; nullptr: not counted)
     uint32_t *blk_total;    // the shadow rays, occluded or not, that blk_counts was taken from (one word)
     float blk[PG_MAX_BLOCKERS][12];
+    // textures (pg_set_textures); all nullptr while none is bound
+    const float4 *tuv;      // PG_TRI_UV_F4 float4 per BVH-order triangle: the vertices' texcoords
+    const GTex *tex;
+    const uint32_t *mtex;   // per material: the texture bound to its diffuse reflectance, ~0 = none
 };
 
 // float4 per training vertex: (x, woPdf), (T after the vertex, packed canonical wo), (L snapshot, -),
@@ -268,6 +272,10 @@ void pg_launch_medium_query(hipStream_t s, const GMedium *medium, int op, const 
                             uint32_t n, float *out);
 void pg_launch_trace_rays(hipStream_t s, const SceneDev &sc, const float *rays, uint32_t n, int any, float *hits,
                           uint32_t *ovf);
+// unit-level texture lookup (pg_texture_query): out[i] = texEval(*tex, uv[i]), n x 3
+void pg_launch_texture_query(hipStream_t s, const GTex *tex, const float *uv, uint32_t n, float *out);
+// closest hits' interpolated uv (pg_hit_uvs): n x 2, (0, 0) for a miss
+void pg_launch_hit_uvs(hipStream_t s, const SceneDev &sc, const float *rays, uint32_t n, float *out, uint32_t *ovf);
 // unit-level blocker test (pg_blocker_test): out[i] = 1 where pg_ray_hits_blockers answers for ray i against sc.blk
 void pg_launch_blocker_test(hipStream_t s, const SceneDev &sc, const float *rays, uint32_t n, uint32_t *out);
 // words of traversal-stack overflow storage for a launch of max_threads (0 = persistent grid)

@@ -614,7 +614,10 @@ extern "C" int pg_debug_watch_read(float *out, uint32_t max, uint32_t *n) {
 #define WSET3(i, v) ((void)0)
 #endif
 
-template <int MODEL, bool CAN_GUIDE, bool ENV>
+// TEX (the textured class, pg_layout.h PG_CLASS_TEXTURED): the vertex's material has a texture as its diffuse
+// reflectance.  The lookup replaces the register copy of GMat::diff and the albedo bound, and the BSDF code runs on
+// that copy unchanged; with TEX = false none of it is compiled.
+template <int MODEL, bool CAN_GUIDE, bool ENV, bool TEX = false>
 __device__ __forceinline__ void shadeOne(const GParams &g, const SceneDev &sc, const SDDev &sd, const PathDev &p,
                                          uint32_t slot, const GMat *mats, bool wantKey, bool &alive, bool &shadow,
                                          bool &probe, uint32_t &rkey, uint32_t &blocked) {
@@ -729,8 +732,20 @@ __device__ __forceinline__ void shadeOne(const GParams &g, const SceneDev &sc, c
             }
         }
 #else
-        const GMat M = mats[h.mat];
+        GMat M = mats[h.mat];
 #endif
+        if constexpr (TEX) {
+            const uint32_t ti = sc.mtex[h.mat];
+            if (ti != 0xFFFFFFFFu) {
+                float tu, tv;
+                hitUV(sc, tri, hv.z, hv.w, tu, tv);
+                const f3 c = texEval(sc.tex[ti], tu, tv);
+                M.diff[0] = c.x;
+                M.diff[1] = c.y;
+                M.diff[2] = c.z;
+                M.wbound = maxc(bsdfAlbedo(M));  // the host's makeGMat bound, of the looked-up reflectance
+            }
+        }
         if ((flags & PF_EMITTED_QUERY) && h.emitter >= 0 && (!g.hide_emitters || (flags & PF_SCATTERED))) {
             loadL();
             L = L + T * Le;
@@ -937,7 +952,7 @@ __device__ __forceinline__ void shadeOne(const GParams &g, const SceneDev &sc, c
 #endif
 }
 
-template <int MODEL, bool CAN_GUIDE, bool ENV>
+template <int MODEL, bool CAN_GUIDE, bool ENV, bool TEX = false>
 __device__ __forceinline__ void shadeBlock(const GParams &g, const SceneDev &sc, const SDDev &sd, const PathDev &p,
                                            const Queue &in, const Queue &out, const Queue &shq, const Queue &pq,
                                            uint32_t bid) {
@@ -962,7 +977,7 @@ __device__ __forceinline__ void shadeBlock(const GParams &g, const SceneDev &sc,
         __syncthreads();
     }
     if (i < n)
-        shadeOne<MODEL, CAN_GUIDE, ENV>(g, sc, sd, p, slot, ldsMats ? reinterpret_cast<const GMat *>(smat) : sc.mats,
+        shadeOne<MODEL, CAN_GUIDE, ENV, TEX>(g, sc, sd, p, slot, ldsMats ? reinterpret_cast<const GMat *>(smat) : sc.mats,
                                         out.keys != nullptr, alive, shadow, probe, rkey, blocked);
     if (out.keys)
         waveAppendKey(alive, slot, (uint16_t)rkey, out.items + (size_t)s * out.stride, out.keys + (size_t)s * out.stride,
@@ -987,10 +1002,10 @@ __device__ __forceinline__ void shadeBlock(const GParams &g, const SceneDev &sc,
     }
 }
 
-template <int MODEL, bool CAN_GUIDE, bool ENV>
+template <int MODEL, bool CAN_GUIDE, bool ENV, bool TEX = false>
 __global__ __launch_bounds__(SHADE_BLOCK) void k_shade(GParams g, SceneDev sc, SDDev sd, PathDev p, Queue in,
                                                        Queue out, Queue shq, Queue pq) {
-    shadeBlock<MODEL, CAN_GUIDE, ENV>(g, sc, sd, p, in, out, shq, pq, blockIdx.x);
+    shadeBlock<MODEL, CAN_GUIDE, ENV, TEX>(g, sc, sd, p, in, out, shq, pq, blockIdx.x);
 }
 
 // every material class of a bounce in one launch (no environment emitter): blocks
@@ -1002,16 +1017,21 @@ struct ShadeRanges {
 #ifndef PG_SHADE_WAVES
 #define PG_SHADE_WAVES 4
 #endif
+// TEX: the scene has textures bound (pg_set_textures): the instantiation with the textured class' body.  Scenes
+// without textures launch k_shade_all<false>, which holds the six bodies it always did and nothing else.
+template <bool TEX>
 __global__ __launch_bounds__(SHADE_BLOCK) __attribute__((amdgpu_waves_per_eu(PG_SHADE_WAVES))) void k_shade_all(
     GParams g, SceneDev sc, SDDev sd, PathDev p, ClassQueues in, Queue out, Queue shq, Queue pq, ShadeRanges r) {
-    static_assert(PG_NUM_CLASSES == 6, "class ranges");
+    static_assert(PG_NUM_CLASSES == 7, "class ranges");
     const uint32_t b = blockIdx.x;
     if (b < r.end[0]) shadeBlock<PG_BSDF_DIFFUSE, true, false>(g, sc, sd, p, in.q[0], out, shq, pq, b);
     else if (b < r.end[1]) shadeBlock<PG_BSDF_ROUGHCONDUCTOR, true, false>(g, sc, sd, p, in.q[1], out, shq, pq, b - r.end[0]);
     else if (b < r.end[2]) shadeBlock<PG_BSDF_ROUGHDIELECTRIC, true, false>(g, sc, sd, p, in.q[2], out, shq, pq, b - r.end[1]);
     else if (b < r.end[3]) shadeBlock<PG_BSDF_PLASTIC, false, false>(g, sc, sd, p, in.q[3], out, shq, pq, b - r.end[2]);
     else if (b < r.end[4]) shadeBlock<PG_BSDF_ROUGHPLASTIC, true, false>(g, sc, sd, p, in.q[4], out, shq, pq, b - r.end[3]);
-    else shadeBlock<-1, false, false>(g, sc, sd, p, in.q[5], out, shq, pq, b - r.end[4]);
+    else if (!TEX || b < r.end[5]) shadeBlock<-1, false, false>(g, sc, sd, p, in.q[5], out, shq, pq, b - r.end[4]);
+    else if constexpr (TEX)
+        shadeBlock<PG_MODELS_DIFFUSE_SLOT, true, false, true>(g, sc, sd, p, in.q[6], out, shq, pq, b - r.end[5]);
 }
 
 // ---- counting sort of a queue's shards by ray order key (PG_RAY_SORT): the next closest-hit launch
@@ -1100,11 +1120,18 @@ __global__ __launch_bounds__(256) void k_rsort_scatter(Queue q, uint32_t *hist, 
 // the bounce-by-bounce loop.  Input: the queue of the bounce just traced (hits already in p.hit).
 // stats: [0] traced segments, [1] escaped segments, [2] shadow rays, [3] culled hits, [4] probed segments (u64,
 // device atomics; a probe is also a segment and either a culled hit or an escape).
-template <bool ENV>
+template <bool ENV, bool TEX>
 __device__ __forceinline__ void tailShade(const GParams &g, const SceneDev &sc, const SDDev &sd, const PathDev &p,
                                           uint32_t slot, uint32_t tri, bool &alive, bool &shadow, bool &probe,
                                           uint32_t &blocked) {
     uint32_t rk = 0;
+    // the textured class: only scenes with textures bound have such triangles, and they run k_tail<.., TEX = true>
+    if constexpr (TEX) {
+        if ((sc.tclass[tri] & PG_TCLASS_MASK) == PG_CLASS_TEXTURED) {
+            shadeOne<PG_MODELS_DIFFUSE_SLOT, true, ENV, true>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, probe, rk, blocked);
+            return;
+        }
+    }
     switch (sc.tclass[tri] & PG_TCLASS_MASK) {
         case PG_CLASS_DIFFUSE: shadeOne<PG_BSDF_DIFFUSE, true, ENV>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, probe, rk, blocked); break;
         case PG_CLASS_ROUGHCONDUCTOR:
@@ -1126,7 +1153,7 @@ __device__ __forceinline__ void tailShade(const GParams &g, const SceneDev &sc, 
 // COUNT: the recording passes' instantiation (shadowRows).  On the sampled rows, one plain add per occluded ray to its
 // triangle's counter and one per shadow ray, occluded or not, to the single total: the one-address pattern that is too
 // slow for the bounce launches' rows, affordable here because the tail holds few paths
-template <bool ENV, bool COUNT = false>
+template <bool ENV, bool COUNT = false, bool TEX = false>
 __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PG_TAIL_WAVES > 0 ? PG_TAIL_WAVES : 1))) void k_tail(GParams g, SceneDev sc, SDDev sd, PathDev p, Queue q,
                                                       unsigned long long *stats) {
     __shared__ uint32_t stack[2 * WIDE_LDS_STACK * TRACE_BLOCK];  // >= LDS_STACK words per thread
@@ -1142,7 +1169,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PG_
         while (tri != 0xFFFFFFFFu) {
             bool alive = false, shadow = false, probe = false;
             uint32_t blocked = 0;
-            tailShade<ENV>(g, sc, sd, p, slot, tri, alive, shadow, probe, blocked);
+            tailShade<ENV, TEX>(g, sc, sd, p, slot, tri, alive, shadow, probe, blocked);
             if (!ENV && blocked) {  // a shadow ray the blocker list resolved: counted, not traced
                 ++shadows;
                 ++drops;
@@ -1234,6 +1261,9 @@ __device__ __forceinline__ bool filmSample(const GParams &g, const SceneDev &sc,
 }
 
 // film: box-filtered accumulation of every layer's sample into its pixel, in sample order
+// TEX: textures are bound (pg_set_textures): the first-hit albedo of a textured material is the looked-up value.
+// Scenes without textures launch k_film<false>, the kernel as it was.
+template <bool TEX>
 __global__ __launch_bounds__(256) void k_film(GParams g, SceneDev sc, PathDev p, const uint32_t *__restrict__ local_pixels,
                                               uint32_t pix_begin, uint32_t npix, uint32_t nlayers,
                                               float4 *__restrict__ film, float4 *__restrict__ sumsq,
@@ -1253,6 +1283,19 @@ __global__ __launch_bounds__(256) void k_film(GParams g, SceneDev sc, PathDev p,
                 const float b0 = 1 - hv.z - hv.w;
                 n = normalize(xyz(s3) * b0 + mk(s3.w, s4.x, s4.y) * hv.z + mk(s4.z, s4.w, s1.w) * hv.w);  // fetchHit's shN
                 a = bsdfAlbedo(sc.mats[__float_as_uint(r[0].w) & 0xFFFFu]);
+                if constexpr (TEX) {
+                    const uint32_t mi = __float_as_uint(r[0].w) & 0xFFFFu, ti = sc.mtex[mi];
+                    if (ti != 0xFFFFFFFFu) {  // a textured reflectance: the albedo of the looked-up value, as shadeOne's
+                        GMat M = sc.mats[mi];
+                        float tu, tv;
+                        hitUV(sc, tri, hv.z, hv.w, tu, tv);
+                        const f3 c = texEval(sc.tex[ti], tu, tv);
+                        M.diff[0] = c.x;
+                        M.diff[1] = c.y;
+                        M.diff[2] = c.z;
+                        a = bsdfAlbedo(M);
+                    }
+                }
             }
             sa = make_float4(sa.x + a.x, sa.y + a.y, sa.z + a.z, sa.w + 1.0f);
             sn = make_float4(sn.x + n.x, sn.y + n.y, sn.z + n.z, 0.0f);
@@ -1667,6 +1710,32 @@ __global__ __launch_bounds__(TRACE_BLOCK) void k_trace_rays(SceneDev sc, const f
     h[3] = v;
 }
 
+// pg_texture_query: texEval on raw uv
+__global__ __launch_bounds__(256) void k_texture_query(const GTex *tex, const float *__restrict__ uv, uint32_t n,
+                                                       float *__restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const f3 c = texEval(*tex, uv[2 * (size_t)i], uv[2 * (size_t)i + 1]);
+    out[3 * (size_t)i] = c.x;
+    out[3 * (size_t)i + 1] = c.y;
+    out[3 * (size_t)i + 2] = c.z;
+}
+// pg_hit_uvs: the closest hit's interpolated uv (hitUV), rows as k_trace_rays'
+__global__ __launch_bounds__(TRACE_BLOCK) void k_hit_uvs(SceneDev sc, const float *__restrict__ rays, uint32_t n,
+                                                         float *__restrict__ out, uint32_t *ovf) {
+    __shared__ uint32_t stack[2 * WIDE_LDS_STACK * TRACE_BLOCK];  // >= LDS_STACK words per thread
+    const TStack stk = threadStack(stack, ovf);
+    const uint32_t i = blockIdx.x * TRACE_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const float *r = rays + 8 * (size_t)i;
+    const f3 o = mk(r[0], r[1], r[2]), d = mk(r[4], r[5], r[6]);
+    float tmax = r[7], u = 0, v = 0, tu = 0, tv = 0;
+    uint32_t tri = 0xFFFFFFFFu;
+    if (traverse<false>(sc.nodes, sc.tris, o, d, r[3], tmax, tri, u, v, stk)) hitUV(sc, tri, u, v, tu, tv);
+    out[2 * (size_t)i] = tu;
+    out[2 * (size_t)i + 1] = tv;
+}
+
 // pg_blocker_test: the shader's blocker test on given rays (rows as k_trace_rays')
 __global__ __launch_bounds__(256) void k_blocker_test(SceneDev sc, const float *__restrict__ rays, uint32_t n,
                                                       uint32_t *__restrict__ out) {
@@ -1791,6 +1860,9 @@ static void launchShade(hipStream_t s, int cls, dim3 grid, const GParams &g, con
         case PG_CLASS_ROUGHPLASTIC:
             hipLaunchKernelGGL((k_shade<PG_BSDF_ROUGHPLASTIC, true, ENV>), grid, block, 0, s, g, sc, sd, p, in, out, shq, pq);
             break;
+        case PG_CLASS_TEXTURED:  // a textured diffuse reflectance (diffuse, plastic, roughplastic at run time)
+            hipLaunchKernelGGL((k_shade<PG_MODELS_DIFFUSE_SLOT, true, ENV, true>), grid, block, 0, s, g, sc, sd, p, in, out, shq, pq);
+            break;
         default:  // delta lobes: conductor, dielectric (runtime switch, never guided)
             hipLaunchKernelGGL((k_shade<-1, false, ENV>), grid, block, 0, s, g, sc, sd, p, in, out, shq, pq);
     }
@@ -1814,7 +1886,8 @@ void pg_launch_shade_all(hipStream_t s, const GParams &g, const SceneDev &sc, co
     }
     for (int c = PG_NUM_CLASSES; c < PG_CLASS_ROWS; ++c) cq.q[c] = class_queues[c];
     if (!total) return;
-    hipLaunchKernelGGL(k_shade_all, dim3(total), dim3(SHADE_BLOCK), 0, s, g, sc, sd, p, cq, out, shq, pq, r);
+    if (sc.mtex) hipLaunchKernelGGL(k_shade_all<true>, dim3(total), dim3(SHADE_BLOCK), 0, s, g, sc, sd, p, cq, out, shq, pq, r);
+    else hipLaunchKernelGGL(k_shade_all<false>, dim3(total), dim3(SHADE_BLOCK), 0, s, g, sc, sd, p, cq, out, shq, pq, r);
 }
 // the recording passes count shadow blockers (sc.blk_counts is set only for them, never with an environment emitter)
 static inline bool blockersCounted(const GParams &g, const SceneDev &sc) { return g.record && sc.blk_counts && !sc.env; }
@@ -1860,6 +1933,12 @@ void pg_launch_tail(hipStream_t s, const GParams &g, const SceneDev &sc, const S
     // at most TRACE_MAX_BLOCKS blocks (a grid-stride loop over each shard): the traversal stacks' overflow
     // ring (threadStack / threadWideStack, stride gridDim.x * TRACE_BLOCK) holds that many threads
     const dim3 grid = shardGrid(max_shard, TRACE_BLOCK, TRACE_MAX_BLOCKS / PG_QSHARDS);
+    if (sc.mtex) {  // textures bound: the instantiations with the textured class' body
+        if (sc.env) hipLaunchKernelGGL((k_tail<true, false, true>), grid, dim3(TRACE_BLOCK), 0, s, g, sc, sd, p, q, stats);
+        else if (blockersCounted(g, sc)) hipLaunchKernelGGL((k_tail<false, true, true>), grid, dim3(TRACE_BLOCK), 0, s, g, sc, sd, p, q, stats);
+        else hipLaunchKernelGGL((k_tail<false, false, true>), grid, dim3(TRACE_BLOCK), 0, s, g, sc, sd, p, q, stats);
+        return;
+    }
     if (sc.env) hipLaunchKernelGGL(k_tail<true>, grid, dim3(TRACE_BLOCK), 0, s, g, sc, sd, p, q, stats);
     else if (blockersCounted(g, sc)) hipLaunchKernelGGL((k_tail<false, true>), grid, dim3(TRACE_BLOCK), 0, s, g, sc, sd, p, q, stats);
     else hipLaunchKernelGGL(k_tail<false>, grid, dim3(TRACE_BLOCK), 0, s, g, sc, sd, p, q, stats);
@@ -1882,8 +1961,12 @@ void pg_launch_film(hipStream_t s, const GParams &g, const SceneDev &sc, const P
                     uint32_t npix, uint32_t nlayers, float4 *film_rgbw, float4 *film_sumsq, float4 *aov_albedo,
                     float4 *aov_normal) {
     if (!npix) return;
-    hipLaunchKernelGGL(k_film, dim3(blocks(npix, 256)), dim3(256), 0, s, g, sc, p, local_pixels, pix_begin, npix, nlayers,
-                       film_rgbw, film_sumsq, aov_albedo, aov_normal);
+    if (sc.mtex)
+        hipLaunchKernelGGL(k_film<true>, dim3(blocks(npix, 256)), dim3(256), 0, s, g, sc, p, local_pixels, pix_begin, npix,
+                           nlayers, film_rgbw, film_sumsq, aov_albedo, aov_normal);
+    else
+        hipLaunchKernelGGL(k_film<false>, dim3(blocks(npix, 256)), dim3(256), 0, s, g, sc, p, local_pixels, pix_begin, npix,
+                           nlayers, film_rgbw, film_sumsq, aov_albedo, aov_normal);
 }
 void pg_launch_film_filtered(hipStream_t s, const GParams &g, const SceneDev &sc, const PathDev &p, const FilmFilter &f,
                              const uint32_t *local_pixels, uint32_t pix_begin, uint32_t npix, uint32_t nlayers,
@@ -1974,6 +2057,12 @@ void pg_launch_trace_rays(hipStream_t s, const SceneDev &sc, const float *rays, 
                           uint32_t *ovf) {
     if (!n) return;
     hipLaunchKernelGGL(k_trace_rays, dim3(blocks(n, TRACE_BLOCK)), dim3(TRACE_BLOCK), 0, s, sc, rays, n, any, hits, ovf);
+}
+void pg_launch_texture_query(hipStream_t s, const GTex *tex, const float *uv, uint32_t n, float *out) {
+    if (n) hipLaunchKernelGGL(k_texture_query, dim3(blocks(n, 256)), dim3(256), 0, s, tex, uv, n, out);
+}
+void pg_launch_hit_uvs(hipStream_t s, const SceneDev &sc, const float *rays, uint32_t n, float *out, uint32_t *ovf) {
+    if (n) hipLaunchKernelGGL(k_hit_uvs, dim3(blocks(n, TRACE_BLOCK)), dim3(TRACE_BLOCK), 0, s, sc, rays, n, out, ovf);
 }
 void pg_launch_blocker_test(hipStream_t s, const SceneDev &sc, const float *rays, uint32_t n, uint32_t *out) {
     if (!n) return;

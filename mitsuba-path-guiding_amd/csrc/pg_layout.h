@@ -59,6 +59,20 @@ struct GEnv {
 };
 static_assert(sizeof(GEnv) == 128, "GEnv layout");
 
+// Texture record: 64 B (pg_set_textures; pg_capi.h pg_texture).  texels: width x height float4 (rgb, 0), row y at
+// texels + 4 * y * width; nullptr for a checkerboard.  mode: type | filter << 4 | wrap_u << 8 | wrap_v << 12.
+struct GTex {
+    const float *texels;
+    uint32_t width, height;
+    uint32_t mode, pad0;
+    float uscale, vscale, uoffset, voffset;
+    float color0[3], color1[3];
+};
+static_assert(sizeof(GTex) == 64, "GTex layout");
+// Per BVH-order triangle uv record (SceneDev::tuv, allocated only while textures are set): t0.xy, t1.xy | t2.xy, 0, 0;
+// 2 x float4 = 32 B, so both 16-B loads stay within one 128-B line.  Without texcoords: (0, 0), (1, 0), (0, 1).
+#define PG_TRI_UV_F4 2
+
 // Heterogeneous medium record: 128 B (volpath).  World -> grid is g = p * gs + go
 // (gridvolume.cpp:186-198); invMax = 1 / (scale * maxFloatValue), maxFloatValue = 1
 // (gridvolume.cpp:583-585, heterogeneous.cpp:236-242).  density: res x*y*z floats, x fastest.
@@ -245,7 +259,11 @@ inline void pg_qnode_box(const float *node, int s, float lo[3], float hi[3]) {
 #define PG_CLASS_PLASTIC 3
 #define PG_CLASS_ROUGHPLASTIC 4
 #define PG_CLASS_DELTA 5
-#define PG_NUM_CLASSES 6
+// materials whose diffuse reflectance is a texture (pg_set_textures), whatever their model: the run-time-model body
+// with the lookup compiled in (shadeOne's TEX flag).  Empty unless textures are bound, so the other classes' bodies
+// never see a textured vertex.
+#define PG_CLASS_TEXTURED 6
+#define PG_NUM_CLASSES 7
 // counted-only rows after the class queues' shard counts: escaped rays, then culled hits (PF_DOOMED below)
 #define PG_CLASS_ESCAPED PG_NUM_CLASSES
 #define PG_CLASS_CULLED (PG_NUM_CLASSES + 1)

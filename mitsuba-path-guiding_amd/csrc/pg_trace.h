@@ -1033,6 +1033,79 @@ __device__ __forceinline__ void fetchHit(const SceneDev &sc, uint32_t tri, float
 }
 
 // ---------------------------------------------------------------------------------------------
+// Textures (pg_capi.h pg_set_textures): the lookup without ray differentials, Texture2D::eval(its, false).
+// Intersection::uv of a hit (skdtree.h:355,398-405): t0 b.x + t1 b.y + t2 b.z with b = (1 - u - v, u, v)
+__device__ __forceinline__ void hitUV(const SceneDev &sc, uint32_t tri, float u, float v, float &tu, float &tv) {
+#pragma clang fp contract(off)
+    tu = u;
+    tv = v;
+    if (!sc.tuv) return;
+    const float4 a = sc.tuv[(size_t)PG_TRI_UV_F4 * tri], b = sc.tuv[(size_t)PG_TRI_UV_F4 * tri + 1];
+    const float b0 = 1 - u - v;
+    tu = a.x * b0 + a.z * u + b.x * v;
+    tv = a.y * b0 + a.w * u + b.y * v;
+}
+// floor of a finite texel coordinate as an int: clamped to +-2^30 first, so the conversion is defined for every
+// finite input and x + 1, 2 W and x mod 2 W below cannot overflow (W, H <= 2^24).  Exact below 2^30.
+__device__ __forceinline__ float texClamp(float x) { return fminf(fmaxf(x, -1073741824.0f), 1073741824.0f); }
+__device__ __forceinline__ int texFloor(float x) { return (int)floorf(texClamp(x)); }
+// TMIPMap::evalTexel at level 0 (mipmap.h:503-563): x wrapped first, then y
+__device__ __forceinline__ bool texWrap(uint32_t wrap, int n, int &x, f3 &constant) {
+    if (x >= 0 && x < n) return true;
+    switch (wrap) {
+        case PG_TEXWRAP_REPEAT:
+            x %= n;
+            if (x < 0) x += n;
+            return true;
+        case PG_TEXWRAP_MIRROR:
+            x %= 2 * n;
+            if (x < 0) x += 2 * n;
+            if (x >= n) x = 2 * n - x - 1;
+            return true;
+        case PG_TEXWRAP_ZERO: constant = mk1(0.f); return false;
+        case PG_TEXWRAP_ONE: constant = mk1(1.f); return false;
+        default: x = min(max(x, 0), n - 1); return true;  // clamp
+    }
+}
+__device__ __forceinline__ f3 texTexel(const GTex &t, int x, int y) {
+    const int w = (int)t.width, h = (int)t.height;
+    f3 c;
+    if (!texWrap((t.mode >> 8) & 0xFu, w, x, c)) return c;
+    if (!texWrap((t.mode >> 12) & 0xFu, h, y, c)) return c;
+    // the address is inside the image whatever the wrap modes made of (x, y)
+    x = min(max(x, 0), w - 1);
+    y = min(max(y, 0), h - 1);
+    const float4 v = reinterpret_cast<const float4 *>(t.texels)[(size_t)y * (uint32_t)w + (uint32_t)x];
+    return mk(v.x, v.y, v.z);
+}
+// the texture's value at the hit's uv: Texture2D::eval's transform (texture.cpp:112-121), then BitmapTexture::eval
+// (bitmap.cpp:431-449: evalBox / evalBilinear at level 0, mipmap.h:566-596) or Checkerboard::eval
+// (checkerboard.cpp:66-74).  Shared by the shading kernels, k_film's first-hit albedo and pg_texture_query.
+__device__ __forceinline__ f3 texEval(const GTex &t, float tu, float tv) {
+#pragma clang fp contract(off)
+    const float u = tu * t.uscale + t.uoffset, v = tv * t.vscale + t.voffset;
+    if (!isfinite(u) || !isfinite(v)) return mk1(0.f);
+    if ((t.mode & 0xFu) == PG_TEXTURE_CHECKERBOARD) {
+        // (int) truncates toward zero; math::modulo is the positive remainder
+        const int ix = (int)fminf(fmaxf(u * 2, -1073741824.0f), 1073741824.0f);
+        const int iy = (int)fminf(fmaxf(v * 2, -1073741824.0f), 1073741824.0f);
+        const int x = 2 * (ix & 1) - 1, y = 2 * (iy & 1) - 1;
+        return x * y == 1 ? mk(t.color0[0], t.color0[1], t.color0[2]) : mk(t.color1[0], t.color1[1], t.color1[2]);
+    }
+    const float fw = (float)t.width, fh = (float)t.height;
+    if (((t.mode >> 4) & 0xFu) == PG_TEXFILTER_NEAREST) return texTexel(t, texFloor(u * fw), texFloor(v * fh));
+    // clamped like the integer part, so a huge coordinate has the weights (1, 0) of an integer one, not inf - inf
+    const float x = texClamp(u * fw - 0.5f), y = texClamp(v * fh - 0.5f);
+    const int xp = texFloor(x), yp = texFloor(y);
+    const float dx1 = x - (float)xp, dx2 = 1.0f - dx1, dy1 = y - (float)yp, dy2 = 1.0f - dy1;
+    const f3 t00 = texTexel(t, xp, yp), t01 = texTexel(t, xp, yp + 1), t10 = texTexel(t, xp + 1, yp),
+             t11 = texTexel(t, xp + 1, yp + 1);
+    return mk(t00.x * dx2 * dy2 + t01.x * dx2 * dy1 + t10.x * dx1 * dy2 + t11.x * dx1 * dy1,
+              t00.y * dx2 * dy2 + t01.y * dx2 * dy1 + t10.y * dx1 * dy2 + t11.y * dx1 * dy1,
+              t00.z * dx2 * dy2 + t01.z * dx2 * dy1 + t10.z * dx1 * dy2 + t11.z * dx1 * dy1);
+}
+
+// ---------------------------------------------------------------------------------------------
 // Environment emitter (src/emitters/envmap.cpp).  Texel lookups follow TMIPMap::evalTexel at level 0
 // (mipmap.h:503-563: repeat in x, clamp in y); the summation orders of evalBilinear (mipmap.h:575-596)
 // and internalSampleDirection / internalPdfDirection (envmap.cpp:567-633) are kept as written.

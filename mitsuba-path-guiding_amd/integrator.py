@@ -120,6 +120,33 @@ class Device:
     def upload(self, scene):
         self.scene = scene
         self._chk(self.lib.pg_upload_scene(self.h, C.byref(scene.desc())))
+        if getattr(scene, "texture_bindings", None):  # pg_upload_scene cleared any textures of an earlier scene
+            self.set_textures(scene.textures, scene.texture_bindings, scene.texcoords)
+
+    def set_textures(self, textures, bindings, texcoords=None):
+        """pg_set_textures: pg_texture records (scenes.make_texture), (material, texture) pairs and per-vertex
+        texcoords of the uploaded scene ((num_vertices, 2), or None: barycentric uv).  After upload, before the
+        first render pass; no bindings turns the textures off."""
+        tex = (capi.pg_texture * max(1, len(textures)))(*textures)
+        bind = (capi.pg_texture_binding * max(1, len(bindings)))(*[capi.pg_texture_binding(m, t) for m, t in bindings])
+        uv = None if texcoords is None else np.ascontiguousarray(texcoords, np.float32)
+        if uv is not None and uv.shape != (self.scene.desc().num_vertices, 2):
+            raise ValueError("texcoords: one (u, v) per vertex of the uploaded scene")
+        self._chk(self.lib.pg_set_textures(self.h, tex, len(textures), bind, len(bindings), _p(uv) if uv is not None else None))
+
+    def texture_query(self, texture, uv):
+        """pg_texture_query: the device lookup of one pg_texture at raw uv (n, 2) -> (n, 3)."""
+        uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+        out = np.zeros((len(uv), 3), np.float32)
+        self._chk(self.lib.pg_texture_query(self.h, C.byref(texture), _p(uv), len(uv), _p(out)))
+        return out
+
+    def hit_uvs(self, rays):
+        """pg_hit_uvs: the closest hits' interpolated uv, (n, 2); (0, 0) for a miss."""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        out = np.zeros((len(rays), 2), np.float32)
+        self._chk(self.lib.pg_hit_uvs(self.h, _p(rays), len(rays), _p(out)))
+        return out
 
     def render_pass(self, spp, sample_offset=0, record=False):
         self._chk(self.lib.pg_render_pass(self.h, spp, sample_offset, int(bool(record))))

@@ -16,6 +16,11 @@ adapter's flatten() produces from Scene::getShapes()/getBSDFs() (INTEGRATION.md)
   bsdf              diffuse, conductor, roughconductor (material Cu / Al / Au / none, or eta + k),
                     dielectric, roughdielectric, plastic, roughplastic (intIOR / extIOR by value or
                     by name: src/bsdfs/ior.h), twosided, null; distribution beckmann / ggx
+  texture           bitmap (.npy / .pfm / .exr linear; 8-bit PNG / JPEG with the sRGB curve or 'gamma'; filterType
+                    nearest / bilinear, ewa and trilinear as bilinear with a warning; wrapMode[U|V]) and
+                    checkerboard, with uscale / vscale / uvscale / uoffset / voffset, as diffuse.reflectance or
+                    plastic / roughplastic diffuseReflectance, nested, inside twosided or through <ref>;
+                    texcoords from obj vt (flipTexCoords, default true), ply s t / u v, serialized
   shape             obj, ply (ascii / binary), serialized (Mitsuba's zlib mesh format, any shapeIndex),
                     rectangle, cube, disk and sphere (tessellated), with
                     toWorld, flipNormals, faceNormals, a nested or referenced bsdf and an area emitter
@@ -35,6 +40,7 @@ import math
 import os
 import re
 import struct
+import warnings
 import xml.etree.ElementTree as ET
 import zlib
 
@@ -109,6 +115,7 @@ class _Loader:
         # (film.cpp:93).  Only recorded: an integrator applies it when asked to (rfilter="scene").
         self.sc.rfilter = ("gaussian", 0.5)
         self.mat_index = {}  # id(pg_material) -> scene material index
+        self.tex_index = {}  # id(pg_texture) -> scene texture index
 
     # -- helpers
     def attr(self, el, name, default=None):
@@ -179,14 +186,68 @@ class _Loader:
     def path(self, p):
         return p if os.path.isabs(p) else os.path.join(self.base, p)
 
+    # -- textures (src/textures/bitmap.cpp, checkerboard.cpp; Texture2D, src/librender/texture.cpp:85-121)
+    def texture(self, el):
+        """<texture type="bitmap" | "checkerboard"> -> pg_texture (scenes.make_texture)"""
+        typ = self.attr(el, "type")
+        P = self.props(el)
+        uv = float(P.get("uvscale", 1.0))
+        kw = dict(uscale=float(P.get("uscale", uv)), vscale=float(P.get("vscale", uv)),
+                  uoffset=float(P.get("uoffset", 0.0)), voffset=float(P.get("voffset", 0.0)))
+        if typ == "checkerboard":
+            c = lambda name, d: tuple(np.broadcast_to(np.asarray(P.get(name, d), np.float64).reshape(-1), 3).tolist())
+            t = scenes.make_texture("checkerboard", color0=c("color0", 0.4), color1=c("color1", 0.2), **kw)
+        elif typ == "bitmap":
+            filt = P.get("filterType", "ewa").lower()  # bitmap.cpp: ewa is the default
+            if filt in ("ewa", "trilinear"):
+                warnings.warn(f"<texture type=\"bitmap\">: filterType '{filt}' is rendered as level-0 bilinear (the "
+                              "reference filters camera-ray hits with ray differentials; later vertices are bilinear "
+                              "there too)")
+                filt = "bilinear"
+            if filt not in ("nearest", "bilinear"):
+                raise NotImplementedError(f"<texture type=\"bitmap\">: filterType '{filt}'")
+            wrap = P.get("wrapMode", "repeat").lower()
+            wu, wv = P.get("wrapModeU", wrap).lower(), P.get("wrapModeV", wrap).lower()
+            for w in (wu, wv):
+                if w not in scenes._TEX_WRAPS:
+                    raise NotImplementedError(f"<texture type=\"bitmap\">: wrapMode '{w}'")
+            rgb = read_texture_image(self.path(P["filename"]), P.get("gamma"))
+            t = scenes.make_texture("bitmap", rgb, filter=filt, wrap=wu, wrap_v=wv, **kw)
+        else:
+            raise NotImplementedError(f"<texture type=\"{typ}\"> (bitmap and checkerboard are supported)")
+        if el.get("id"):
+            self.ids[el.get("id")] = t
+        return t
+
     # -- BSDFs (src/bsdfs/*.cpp constructors)
     def bsdf(self, el):
         typ = self.attr(el, "type")
         P = self.props(el)
-        nested = [c for c in el if c.tag == "bsdf" or c.tag == "ref"]
+        nested = [c for c in el if c.tag == "bsdf" or (c.tag == "ref" and
+                                                       not isinstance(self.ids.get(c.get("id")), capi.pg_texture))]
+        # a texture as the diffuse reflectance of diffuse / plastic / roughplastic; any other textured parameter raises
+        slot = {"diffuse": "reflectance", "plastic": "diffuseReflectance", "roughplastic": "diffuseReflectance"}.get(typ)
+        tex = None
         for c in el:
-            if c.tag == "texture":
-                raise NotImplementedError(f"<bsdf type=\"{typ}\">: textures are out of scope (constant albedos only)")
+            is_ref = c.tag == "ref" and isinstance(self.ids.get(c.get("id")), capi.pg_texture)
+            if c.tag != "texture" and not is_ref:
+                continue
+            name = self.attr(c, "name")
+            if slot is None or name != slot:
+                raise NotImplementedError(f"<bsdf type=\"{typ}\">: a texture as '{name}' is out of scope (textures are "
+                                          "supported as diffuse.reflectance and plastic / roughplastic diffuseReflectance)")
+            tex = self.ids[c.get("id")] if is_ref else self.texture(c)
+        if tex is not None:  # the constant the material keeps: Texture::getAverage
+            if tex.type == capi.PG_TEXTURE_BITMAP:
+                P[slot] = tex._rgb.reshape(-1, 3).mean(0, dtype=np.float64)
+            else:
+                P[slot] = (np.asarray(list(tex.color0), np.float64) + np.asarray(list(tex.color1), np.float64)) / 2
+            m = self._bsdf(typ, P, nested)
+            m._texture = tex
+            return m
+        return self._bsdf(typ, P, nested)
+
+    def _bsdf(self, typ, P, nested):
 
         def ior(name, default):
             v = P.get(name, default)
@@ -210,6 +271,8 @@ class _Loader:
             m = self.child_bsdf(nested[0])
             m2 = capi.pg_material.from_buffer_copy(m)
             m2.flags |= capi.PG_MAT_TWOSIDED
+            if getattr(m, "_texture", None) is not None:
+                m2._texture = m._texture
             return m2
         if typ == "diffuse":
             return scenes.material("diffuse", reflectance=rgb("reflectance", 0.5))
@@ -267,14 +330,23 @@ class _Loader:
         k = id(m)
         if k not in self.mat_index:
             self.mat_index[k] = self.sc.add_material(m)
+            tex = getattr(m, "_texture", None)
+            if tex is not None:
+                if id(tex) not in self.tex_index:
+                    self.tex_index[id(tex)] = len(self.sc.textures)
+                    self.sc.textures.append(tex)
+                self.sc.bind_texture(self.mat_index[k], self.tex_index[id(tex)])
         return self.mat_index[k]
 
     # -- meshes
     def mesh(self, el, typ, P):
+        UV = None
         if typ == "obj":
-            V, F, N = _read_obj(self.path(P["filename"]))
+            V, F, N, UV = _read_obj(self.path(P["filename"]), texcoords=True)
+            if UV is not None and P.get("flipTexCoords", True):  # obj.cpp: v -> 1 - v by default
+                UV = np.stack([UV[:, 0], 1.0 - UV[:, 1]], 1)
         elif typ == "ply":
-            V, F, N = _read_ply(self.path(P["filename"]))
+            V, F, N, UV = _read_ply(self.path(P["filename"]), texcoords=True)
         elif typ == "rectangle":  # src/shapes/rectangle.cpp: [-1, 1]^2 at z = 0, normal +z
             V = np.array([[-1, -1, 0], [1, -1, 0], [1, 1, 0], [-1, 1, 0]], np.float64)
             F = np.array([[0, 1, 2], [2, 3, 0]])
@@ -312,9 +384,10 @@ class _Loader:
             if "maxSmoothAngle" in P:
                 self.unsupported("shape", typ, "maxSmoothAngle (TriMesh::rebuildTopology) is not restated; "
                                  "the file's normals or smooth vertex normals are used")
-            V, F, N = read_serialized(self.path(P["filename"]), int(P.get("shapeIndex", 0)))
+            V, F, N, UV = read_serialized(self.path(P["filename"]), int(P.get("shapeIndex", 0)), texcoords=True)
         else:
             return None
+        self._uv = UV
         V, F = np.asarray(V, np.float64), np.asarray(F, np.int64)
         M = P.get("toWorld", np.eye(4))
         V = V @ M[:3, :3].T + M[:3, 3]
@@ -346,6 +419,7 @@ class _Loader:
         if res is None:
             return self.unsupported("shape", typ, "unknown shape plugin")
         V, F, N = res
+        UV = self._uv
         mat = None
         radiance = None
         sides = {"interior": -1, "exterior": -1}
@@ -381,7 +455,8 @@ class _Loader:
                 mat = scenes.material("diffuse", reflectance=(0.5, 0.5, 0.5))
         m = self.material_index(mat)
         self.sc.add_mesh(V.astype(np.float32), F.astype(np.uint32), None if N is None else N.astype(np.float32),
-                         material=m, radiance=radiance, interior=sides["interior"], exterior=sides["exterior"])
+                         material=m, radiance=radiance, interior=sides["interior"], exterior=sides["exterior"],
+                         uv=None if UV is None else UV.astype(np.float32))
 
     # -- participating media (src/medium/homogeneous.cpp, materials.h:90-195 lookupMaterial)
     def medium(self, el):
@@ -533,7 +608,9 @@ class _Loader:
                     if self.strict:
                         raise
                     self.out.skipped.append(("medium", self.attr(el, "type"), str(e)))
-            elif el.tag in ("phase", "texture"):
+            elif el.tag == "texture":
+                self.texture(el)
+            elif el.tag == "phase":
                 self.unsupported(el.tag, self.attr(el, "type"), "not flattened by this loader")
         return self.out
 
@@ -578,11 +655,12 @@ def _vertex_normals(V, F):
     return np.where(ln > 0, N / np.maximum(ln, 1e-300), np.array([1.0, 0.0, 0.0]))
 
 
-def _read_obj(path):
-    """Wavefront OBJ (src/shapes/obj.cpp): v / vn / f (polygons fanned); vertices are welded by
-    their (position, normal) index pair."""
-    P, Nn, keys, faces = [], [], {}, []
-    has_n = False
+def _read_obj(path, texcoords=False):
+    """Wavefront OBJ (src/shapes/obj.cpp): v / vt / vn / f (polygons fanned); vertices are welded by
+    their (position, texcoord, normal) index triple.  texcoords=True also returns the (n, 2) vt array as
+    written in the file (no flip), or None."""
+    P, Nn, Tt, keys, faces = [], [], [], {}, []
+    has_n = has_t = False
     with open(path) as f:
         for line in f:
             t = line.split()
@@ -592,18 +670,24 @@ def _read_obj(path):
                 P.append([float(x) for x in t[1:4]])
             elif t[0] == "vn":
                 Nn.append([float(x) for x in t[1:4]])
+            elif t[0] == "vt":
+                Tt.append([float(x) for x in t[1:3]])
             elif t[0] == "f":
                 idx = []
                 for w in t[1:]:
                     parts = w.split("/")
                     vi = int(parts[0])
                     vi = vi - 1 if vi > 0 else len(P) + vi
-                    ni = -1
+                    ni = ti = -1
+                    if len(parts) >= 2 and parts[1]:
+                        ti = int(parts[1])
+                        ti = ti - 1 if ti > 0 else len(Tt) + ti
+                        has_t = True
                     if len(parts) >= 3 and parts[2]:
                         ni = int(parts[2])
                         ni = ni - 1 if ni > 0 else len(Nn) + ni
                         has_n = True
-                    k = (vi, ni)
+                    k = (vi, ni, ti)
                     if k not in keys:
                         keys[k] = len(keys)
                     idx.append(keys[k])
@@ -612,7 +696,10 @@ def _read_obj(path):
     order = sorted(keys.items(), key=lambda kv: kv[1])
     V = np.array([P[k[0]] for k, _ in order], np.float64)
     N = np.array([Nn[k[1]] if k[1] >= 0 else [0, 0, 0] for k, _ in order], np.float64) if has_n else None
-    return V, np.array(faces, np.int64), N
+    if not texcoords:
+        return V, np.array(faces, np.int64), N
+    UV = np.array([Tt[k[2]] if k[2] >= 0 else [0, 0] for k, _ in order], np.float64) if has_t else None
+    return V, np.array(faces, np.int64), N, UV
 
 
 # TriMesh serialization flags (trimesh.cpp:89-97) and file header (trimesh.cpp:34-36)
@@ -621,13 +708,13 @@ _SER_NORMALS, _SER_TEXCOORDS, _SER_COLORS, _SER_FACE_NORMALS = 0x0001, 0x0002, 0
 _SER_SINGLE, _SER_DOUBLE = 0x1000, 0x2000
 
 
-def read_serialized(path, index=0):
+def read_serialized(path, index=0, texcoords=False):
     """Mesh `index` of a Mitsuba .serialized file (TriMesh::loadCompressed / readHeader / readOffset,
     trimesh.cpp:175-294): a little-endian (u16 0x041C, u16 version) header, then a zlib stream of
     u32 flags, [v4: NUL-terminated name], u64 vertex and triangle counts, positions, [normals],
     [texcoords], [colors] (f32 or f64 by flag) and u32 triangle indices.  Files with several meshes
     end with a dictionary of per-mesh byte offsets (u64 in v4, u32 in v3) and a u32 mesh count.
-    Returns (V, F, N or None) as float64 / int64 arrays."""
+    Returns (V, F, N or None) as float64 / int64 arrays; with texcoords=True also the (n, 2) texcoord block or None."""
     with open(path, "rb") as f:
         data = f.read()
 
@@ -669,14 +756,13 @@ def read_serialized(path, index=0):
 
     V = take(ft, 3 * nv).reshape(nv, 3).astype(np.float64)
     N = take(ft, 3 * nv).reshape(nv, 3).astype(np.float64) if flags & _SER_NORMALS else None
-    if flags & _SER_TEXCOORDS:
-        take(ft, 2 * nv)
+    UV = take(ft, 2 * nv).reshape(nv, 2).astype(np.float64) if flags & _SER_TEXCOORDS else None
     if flags & _SER_COLORS:
         take(ft, 3 * nv)
     F = take(np.dtype("<u4"), 3 * nt).reshape(nt, 3).astype(np.int64)
     if nv and (F.min() < 0 or F.max() >= nv):
         raise ValueError(f"{path}: triangle index out of range")
-    return V, F, N
+    return (V, F, N, UV) if texcoords else (V, F, N)
 
 
 def write_serialized(path, meshes):
@@ -704,8 +790,10 @@ _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short":
               "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
 
 
-def _read_ply(path):
-    """Stanford PLY (src/shapes/ply.cpp): ascii or binary, vertex x y z [nx ny nz], face vertex lists."""
+def _read_ply(path, texcoords=False):
+    """Stanford PLY (src/shapes/ply.cpp): ascii or binary, vertex x y z [nx ny nz] [s t | u v], face vertex lists.
+    texcoords=True also returns the (n, 2) texcoords or None."""
+    uv_out = []
     with open(path, "rb") as f:
         data = f.read()
     end = data.index(b"end_header") + len(b"end_header")
@@ -741,7 +829,7 @@ def _read_ply(path):
                         row.append(float(toks[pos]))
                         pos += 1
                 rows.append(row)
-            V, F, N = _ply_collect(name, props, rows, V, F, N)
+            V, F, N = _ply_collect(name, props, rows, V, F, N, uv_out)
     else:
         endian = "<" if fmt == "binary_little_endian" else ">"
         pos = 0
@@ -767,12 +855,20 @@ def _read_ply(path):
                             row.append(float(np.frombuffer(body, endian + t, 1, pos)[0]))
                             pos += np.dtype(t).itemsize
                     rows.append(row)
-            V, F, N = _ply_collect(name, props, rows, V, F, N)
-    return V, F, N
+            V, F, N = _ply_collect(name, props, rows, V, F, N, uv_out)
+    return (V, F, N, uv_out[0] if uv_out else None) if texcoords else (V, F, N)
 
 
-def _ply_collect(name, props, rows, V, F, N):
+def _ply_collect(name, props, rows, V, F, N, uv_out=None):
     names = [p[-1] for p in props]
+    if name == "vertex" and uv_out is not None:
+        for a, b in (("s", "t"), ("u", "v")):
+            if a in names and b in names:
+                if isinstance(rows, np.ndarray):
+                    uv_out.append(np.stack([rows[a].astype(np.float64), rows[b].astype(np.float64)], 1))
+                else:
+                    uv_out.append(np.array(rows, np.float64)[:, [names.index(a), names.index(b)]])
+                break
     if name == "vertex":
         if isinstance(rows, np.ndarray):
             V = np.stack([rows[k].astype(np.float64) for k in "xyz"], 1)
@@ -812,6 +908,23 @@ def read_image(path):
     if ext == ".exr":
         return _read_exr(path)
     raise NotImplementedError(f"image format {ext}")
+
+
+def read_texture_image(path, gamma=None):
+    """Texels of a bitmap texture, (H, W, 3) linear float32, row 0 = the image's first row (v = 0): .npy, .pfm and
+    .exr through read_image (linear); 8-bit PNG / JPEG through PIL with the sRGB curve, or value^gamma when `gamma`
+    is given and positive (bitmap.cpp 'gamma')."""
+    ext = os.path.splitext(path)[1].lower()
+    if ext in (".npy", ".pfm", ".exr"):
+        a = read_image(path)
+        return np.ascontiguousarray(np.repeat(a[..., None], 3, 2) if a.ndim == 2 else a[..., :3], np.float32)
+    if ext in (".png", ".jpg", ".jpeg"):
+        from PIL import Image
+        with Image.open(path) as im:
+            a = np.asarray(im.convert("RGB"), np.float64) / 255.0
+        a = _srgb_to_linear(a) if gamma is None or gamma <= 0 else a ** float(gamma)
+        return np.ascontiguousarray(a, np.float32)
+    raise NotImplementedError(f"texture image format {ext}")
 
 
 def _read_exr(path):
@@ -884,11 +997,30 @@ def _rgb_el(name, v):
     return f'<rgb name="{name}" value="{v[0]!r}, {v[1]!r}, {v[2]!r}"/>'
 
 
-def _bsdf_xml(m):
+_FILTER_NAMES = {v: k for k, v in scenes._TEX_FILTERS.items()}
+_WRAP_NAMES = {v: k for k, v in scenes._TEX_WRAPS.items()}
+
+
+def _texture_xml(t, name, fn):
+    """<texture> element of a pg_texture; fn: the file its texels were written to (bitmap)"""
+    f32 = lambda x: float(np.float32(x))
+    xf = "".join(f'<float name="{k}" value="{f32(getattr(t, k))!r}"/>' for k in ("uscale", "vscale", "uoffset", "voffset"))
+    if t.type == capi.PG_TEXTURE_CHECKERBOARD:
+        return (f'<texture type="checkerboard" name="{name}">{_rgb_el("color0", [f32(x) for x in t.color0])}'
+                f'{_rgb_el("color1", [f32(x) for x in t.color1])}{xf}</texture>')
+    return (f'<texture type="bitmap" name="{name}"><string name="filename" value="{fn}"/>'
+            f'<string name="filterType" value="{_FILTER_NAMES[t.filter]}"/>'
+            f'<string name="wrapModeU" value="{_WRAP_NAMES[t.wrap_u]}"/>'
+            f'<string name="wrapModeV" value="{_WRAP_NAMES[t.wrap_v]}"/>{xf}</texture>')
+
+
+def _bsdf_xml(m, tex=None):
     kind = _KIND[m.type]
     body = []
     f32 = lambda x: float(np.float32(x))
-    if kind == "diffuse":
+    if tex is not None:  # the diffuse reflectance is a texture (save)
+        body.append(tex)
+    if kind == "diffuse" and tex is None:
         body.append(_rgb_el("reflectance", [f32(x) for x in m.diffuse_reflectance[:3]]))
     if kind in ("conductor", "roughconductor"):
         body.append(_rgb_el("eta", [f32(x) for x in m.eta[:3]]))
@@ -902,7 +1034,8 @@ def _bsdf_xml(m):
         body.append(_rgb_el("specularReflectance", [f32(x) for x in m.specular_reflectance[:3]]))
         body.append(_rgb_el("specularTransmittance", [f32(x) for x in m.specular_transmittance[:3]]))
     if kind in ("plastic", "roughplastic"):
-        body.append(_rgb_el("diffuseReflectance", [f32(x) for x in m.diffuse_reflectance[:3]]))
+        if tex is None:
+            body.append(_rgb_el("diffuseReflectance", [f32(x) for x in m.diffuse_reflectance[:3]]))
         body.append(_rgb_el("specularReflectance", [f32(x) for x in m.specular_reflectance[:3]]))
         body.append(f'<boolean name="nonlinear" value="{"true" if m.flags & capi.PG_MAT_NONLINEAR else "false"}"/>')
     if kind.startswith("rough"):
@@ -941,6 +1074,16 @@ def save(scene, path, spp=64, integrator="path"):
                f'<sampler type="independent"><integer name="sampleCount" value="{int(spp)}"/></sampler>'
                f'<film type="hdrfilm"><integer name="width" value="{cam.width}"/><integer name="height" '
                f'value="{cam.height}"/><rfilter type="box"/></film></sensor>')
+    UV = sc.texcoords
+    bound = dict(sc.texture_bindings)
+    tex_files = {}
+    for ti, t in enumerate(sc.textures):  # bitmaps as PFM (bottom row first)
+        if t.type == capi.PG_TEXTURE_BITMAP and ti in bound.values():
+            tex_files[ti] = f"{stem}_texture{ti}.pfm"
+            img = np.ascontiguousarray(t._rgb[::-1], "<f4")
+            with open(os.path.join(d, tex_files[ti]), "wb") as f:
+                f.write(b"PF\n%d %d\n-1.0\n" % (img.shape[1], img.shape[0]))
+                f.write(img.tobytes())
     for si, sh in enumerate(sc.shapes):
         F = I[sh.tri_begin:sh.tri_begin + sh.tri_count].astype(np.int64)
         used = np.unique(F)
@@ -952,14 +1095,26 @@ def save(scene, path, spp=64, integrator="path"):
                 f.write(f"v {float(p[0])!r} {float(p[1])!r} {float(p[2])!r}\n")
             for n in N[used]:
                 f.write(f"vn {float(n[0])!r} {float(n[1])!r} {float(n[2])!r}\n")
+            if UV is not None:
+                for t in UV[used]:
+                    f.write(f"vt {float(t[0])!r} {float(t[1])!r}\n")
             for t in remap[F] + 1:
-                f.write(f"f {t[0]}//{t[0]} {t[1]}//{t[1]} {t[2]}//{t[2]}\n")
+                if UV is not None:
+                    f.write(f"f {t[0]}/{t[0]}/{t[0]} {t[1]}/{t[1]}/{t[1]} {t[2]}/{t[2]}/{t[2]}\n")
+                else:
+                    f.write(f"f {t[0]}//{t[0]} {t[1]}//{t[1]} {t[2]}//{t[2]}\n")
         em = ""
         if sh.emitter >= 0:
             r = f32l(sc.emitters[sh.emitter].radiance[:3])
             em = f'<emitter type="area">{_rgb_el("radiance", r)}</emitter>'
-        out.append(f'<shape type="obj"><string name="filename" value="{fn}"/>'
-                   f'{_bsdf_xml(sc.materials[sh.material])}{em}</shape>')
+        tex = None
+        if sh.material in bound:
+            m = sc.materials[sh.material]
+            slot = "reflectance" if m.type == capi.PG_BSDF_DIFFUSE else "diffuseReflectance"
+            tex = _texture_xml(sc.textures[bound[sh.material]], slot, tex_files.get(bound[sh.material]))
+        flip = '<boolean name="flipTexCoords" value="false"/>' if UV is not None else ""
+        out.append(f'<shape type="obj"><string name="filename" value="{fn}"/>{flip}'
+                   f'{_bsdf_xml(sc.materials[sh.material], tex)}{em}</shape>')
     if sc.envmap is not None:
         fn = f"{stem}_envmap.pfm"
         img = np.ascontiguousarray(sc._env_rgb[::-1], "<f4")

@@ -94,6 +94,10 @@ class Scene:
         self._env_rgb = None
         self._desc = None
         self.name = "scene"
+        # textures (pg_set_textures): per-mesh texcoords (None: none given), pg_texture records, (material, texture)
+        self._uv = []
+        self.textures = []
+        self.texture_bindings = []
 
     # -- construction
     def add_material(self, m):
@@ -118,10 +122,17 @@ class Scene:
         self.media.append(m)
         return len(self.media) - 1
 
-    def add_mesh(self, V, F, N=None, material=0, radiance=None, interior=-1, exterior=-1):
+    def add_mesh(self, V, F, N=None, material=0, radiance=None, interior=-1, exterior=-1, uv=None):
+        """`uv`: per-vertex texture coordinates (len(V), 2), or None (a textured material then sees the hit's
+        barycentrics, Intersection::uv of a mesh without texcoords)."""
         V = np.asarray(V, np.float32).reshape(-1, 3)
         F = np.asarray(F, np.uint32).reshape(-1, 3)
+        if uv is not None:
+            uv = np.asarray(uv, np.float32).reshape(-1, 2)
+            assert len(uv) == len(V)
         if N is None:  # flat shading: unshare vertices, per-face normals
+            if uv is not None:
+                uv = uv[F].reshape(-1, 2)
             tri = V[F]  # (T,3,3)
             fn = np.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0])
             fn /= np.maximum(np.linalg.norm(fn, axis=1, keepdims=True), 1e-30)
@@ -132,6 +143,7 @@ class Scene:
         tri_begin = sum(len(f) for f in self._idx)
         self._pos.append(V)
         self._nrm.append(N)
+        self._uv.append(uv)
         self._idx.append(F + np.uint32(self._nverts))
         self._nverts += len(V)
         sh = capi.pg_shape(tri_begin, len(F), material, -1, interior, exterior)
@@ -158,6 +170,28 @@ class Scene:
         self._env_rgb = rgb
         self.envmap = e
         self._desc = None
+
+    def add_texture(self, kind, rgb=None, filter="bilinear", wrap="repeat", wrap_v=None, uscale=1.0, vscale=1.0,
+                    uoffset=0.0, voffset=0.0, color0=(0.4, 0.4, 0.4), color1=(0.2, 0.2, 0.2), average=None):
+        """A texture for bind_texture.  kind "bitmap": `rgb` of shape (height, width, 3), linear float32, row 0 at
+        v = 0 (BitmapTexture at MIP level 0); filter "nearest" / "bilinear"; wrap (and wrap_v, if it differs)
+        "repeat" / "clamp" / "mirror" / "zero" / "one".  kind "checkerboard": color0 / color1 (checkerboard.cpp).
+        `average`: Texture::getAverage if the caller has it (plastic's specular sampling weight); else computed."""
+        self.textures.append(make_texture(kind, rgb, filter, wrap, wrap_v, uscale, vscale, uoffset, voffset, color0,
+                                          color1, average))
+        return len(self.textures) - 1
+
+    def bind_texture(self, material, texture):
+        """The diffuse reflectance of `material` (diffuse, plastic, roughplastic) is `texture`."""
+        self.texture_bindings.append((int(material), int(texture)))
+
+    @property
+    def texcoords(self):
+        """(num_vertices, 2) float32, or None when no mesh has texcoords (meshes without get zeros)."""
+        if all(u is None for u in self._uv):
+            return None
+        return np.ascontiguousarray(np.concatenate([u if u is not None else np.zeros((len(p), 2), np.float32)
+                                                    for u, p in zip(self._uv, self._pos)]), np.float32)
 
     def set_camera(self, origin, target, up, fov_x, width, height, near=1e-2, far=1e4):
         c = capi.pg_camera()
@@ -216,6 +250,36 @@ class Scene:
     def bounds(self):
         p = self.positions
         return p.min(0), p.max(0)
+
+
+_TEX_FILTERS = {"nearest": capi.PG_TEXFILTER_NEAREST, "bilinear": capi.PG_TEXFILTER_BILINEAR}
+_TEX_WRAPS = {"repeat": capi.PG_TEXWRAP_REPEAT, "clamp": capi.PG_TEXWRAP_CLAMP, "mirror": capi.PG_TEXWRAP_MIRROR,
+              "zero": capi.PG_TEXWRAP_ZERO, "one": capi.PG_TEXWRAP_ONE}
+
+
+def make_texture(kind, rgb=None, filter="bilinear", wrap="repeat", wrap_v=None, uscale=1.0, vscale=1.0, uoffset=0.0,
+                 voffset=0.0, color0=(0.4, 0.4, 0.4), color1=(0.2, 0.2, 0.2), average=None):
+    """pg_texture record (Scene.add_texture's arguments); keeps its texel array alive as `_rgb`."""
+    t = capi.pg_texture()
+    t._rgb = None
+    if kind == "bitmap":
+        t._rgb = np.ascontiguousarray(rgb, np.float32)
+        assert t._rgb.ndim == 3 and t._rgb.shape[2] == 3
+        t.type = capi.PG_TEXTURE_BITMAP
+        t.height, t.width = t._rgb.shape[0], t._rgb.shape[1]
+        t.rgb = t._rgb.ctypes.data_as(C.POINTER(C.c_float))
+    elif kind == "checkerboard":
+        t.type = capi.PG_TEXTURE_CHECKERBOARD
+    else:
+        raise ValueError(f"unknown texture kind {kind!r}")
+    t.filter = _TEX_FILTERS[filter]
+    t.wrap_u = _TEX_WRAPS[wrap]
+    t.wrap_v = _TEX_WRAPS[wrap if wrap_v is None else wrap_v]
+    t.uscale, t.vscale, t.uoffset, t.voffset = uscale, vscale, uoffset, voffset
+    t.color0 = (C.c_float * 3)(*color0)
+    t.color1 = (C.c_float * 3)(*color1)
+    t.average = (C.c_float * 3)(*(average if average is not None else (-1.0, -1.0, -1.0)))
+    return t
 
 
 # ---------------------------------------------------------------------------------------------

@@ -17,6 +17,7 @@
 #include <mitsuba/render/progressiveintegrator.h>
 #include <mitsuba/render/scene.h>
 #include <mitsuba/render/trimesh.h>
+#include <mitsuba/render/texture.h>
 #include <mitsuba/render/medium.h>
 #include <mitsuba/render/phase.h>
 #include <mitsuba/render/sensor.h>
@@ -122,6 +123,10 @@ public:
         m_flat = flatten(scene);  // TriMesh arrays, BSDFs, emitters (area + environment), media, camera
         m_flat.bind();            // the descriptor's pointers into this copy's arrays
         check(pg_upload_scene(m_ctx, &m_flat.desc));
+        // textured diffuse reflectances (flattenTexture) with the meshes' texcoords; after the upload, before any pass
+        if (!m_flat.bindings.empty())
+            check(pg_set_textures(m_ctx, m_flat.textures.data(), (uint32_t) m_flat.textures.size(), m_flat.bindings.data(),
+                                  (uint32_t) m_flat.bindings.size(), m_flat.hasUV ? m_flat.uv.data() : NULL));
         // the film's reconstruction filter: any separable filter through its own discretised table
         // (rfilter.h:76-77); the box keeps the per-pixel film
         const ReconstructionFilter *rf = scene->getSensor()->getFilm()->getReconstructionFilter();
@@ -389,6 +394,13 @@ protected:
         pg_envmap env;
         std::vector<pg_medium> media;
         std::vector<std::vector<float>> densities;  // per medium, [z][y][x], values in [0, 1]
+        // textures bound to diffuse reflectances (pg_set_textures): records, their texels (float RGB, row 0 = v 0),
+        // (material, texture) pairs and the per-vertex texcoords of pos (zeros for meshes without)
+        std::vector<pg_texture> textures;
+        std::vector<std::vector<float>> texels;
+        std::vector<pg_texture_binding> bindings;
+        std::vector<float> uv;
+        bool hasUV = false;
         bool mirrorX = false, hasEnv = false;
         void bind() {  // pg_upload_scene copies everything; the arrays live until then
             desc.num_vertices = (uint32_t) (pos.size() / 3);
@@ -407,9 +419,12 @@ protected:
             desc.media = media.empty() ? NULL : media.data();
             env.rgb = envRGB.data();
             desc.envmap = hasEnv ? &env : NULL;
+            for (size_t t = 0; t < textures.size(); ++t) textures[t].rgb = texels[t].empty() ? NULL : texels[t].data();
         }
     };
     Flattened flatten(const Scene *scene) const;
+    void flattenTexture(const BSDF *bsdf, uint32_t material, std::map<const Texture *, uint32_t> &texIndex,
+                        Flattened &f) const;
     pg_material material(const BSDF *bsdf) const;
     void flattenEnvironment(const Scene *scene, Flattened &f) const;
     int32_t flattenMedium(const Medium *medium, const AABB &bounds, Flattened &f,
@@ -511,6 +526,76 @@ inline pg_material GuidedGPUIntegrator::material(const BSDF *bsdf) const {
 // float RGB (latitude-longitude, row 0 at theta = 0), the rotation of toWorld and `scale`
 // (envmap.cpp:100-190); a constant emitter (constant.cpp:49) becomes a uniform bitmap.  The library
 // builds the sampling CDFs itself (EnvironmentMap::configure, envmap.cpp:260-329).
+// A Texture as diffuse.reflectance / plastic, roughplastic diffuseReflectance (BSDF::getDiffuseReflectanceTexture,
+// bsdf.h:557): 'bitmap' (bitmap.cpp) gives its level-0 bitmap (getBitmap), filterType, wrapMode[U|V] and the
+// Texture2D uv transform from its Properties, 'checkerboard' (checkerboard.cpp) its two colours; getAverage() is
+// passed on (plastic.cpp:201-202).  ewa / trilinear are passed as bilinear (include/pg_capi.h "textures").  A
+// constant texture stays the constant material() read; any other texture plugin ends the job.
+inline void GuidedGPUIntegrator::flattenTexture(const BSDF *bsdf, uint32_t material,
+                                                std::map<const Texture *, uint32_t> &texIndex, Flattened &f) const {
+    if (bsdf->getClass()->getName() == "TwoSidedBRDF") bsdf = bsdf->getNestedBSDF(0).get();
+    const BSDF::EBSDFModel model = bsdf->getModel();
+    if (model != BSDF::EMSmoothDiffuse && model != BSDF::EMPlastic && model != BSDF::EMRoughPlastic) return;
+    ref<Texture> tex = bsdf->getDiffuseReflectanceTexture();
+    if (!tex || tex->isConstant()) return;
+    if (!texIndex.count(tex.get())) {
+        const Properties &p = tex->getProperties();
+        const std::string cls = tex->getClass()->getName();
+        pg_texture t;
+        memset(&t, 0, sizeof(t));
+        std::vector<float> rgb;
+        auto wrapOf = [&](const std::string &w) -> uint32_t {
+            if (w == "repeat") return PG_TEXWRAP_REPEAT;
+            if (w == "clamp") return PG_TEXWRAP_CLAMP;
+            if (w == "mirror") return PG_TEXWRAP_MIRROR;
+            if (w == "zero") return PG_TEXWRAP_ZERO;
+            if (w == "one") return PG_TEXWRAP_ONE;
+            Log(EError, "guided_gpu: texture wrap mode '%s' is not supported", w.c_str());
+            return PG_TEXWRAP_REPEAT;
+        };
+        if (cls == "BitmapTexture") {
+            ref<Bitmap> bmp = tex->getBitmap()->convert(Bitmap::ERGB, Bitmap::EFloat32);
+            t.type = PG_TEXTURE_BITMAP;
+            t.width = (uint32_t) bmp->getWidth();
+            t.height = (uint32_t) bmp->getHeight();
+            const float *src = bmp->getFloat32Data();
+            rgb.assign(src, src + (size_t) 3 * t.width * t.height);
+            for (float &x : rgb) x = std::max(x, 0.0f);   // the MIP map clamps negative texels (mipmap.h:232-240)
+            t.filter = boost::to_lower_copy(p.getString("filterType", "ewa")) == "nearest" ? PG_TEXFILTER_NEAREST
+                                                                                           : PG_TEXFILTER_BILINEAR;
+            const std::string wrap = boost::to_lower_copy(p.getString("wrapMode", "repeat"));
+            t.wrap_u = wrapOf(boost::to_lower_copy(p.getString("wrapModeU", wrap)));
+            t.wrap_v = wrapOf(boost::to_lower_copy(p.getString("wrapModeV", wrap)));
+        } else if (cls == "Checkerboard") {
+            t.type = PG_TEXTURE_CHECKERBOARD;
+            float c0[4], c1[4];
+            pgRGB(p.getSpectrum("color0", Spectrum(0.4f)), c0);
+            pgRGB(p.getSpectrum("color1", Spectrum(0.2f)), c1);
+            for (int a = 0; a < 3; ++a) {
+                t.color0[a] = c0[a];
+                t.color1[a] = c1[a];
+            }
+        } else {
+            Log(EError, "guided_gpu: texture '%s' is not supported (bitmap and checkerboard are)", cls.c_str());
+        }
+        const Float uvscale = p.getFloat("uvscale", 1.0f);   // Texture2D::Texture2D (texture.cpp:85-100)
+        t.uscale = (float) p.getFloat("uscale", uvscale);
+        t.vscale = (float) p.getFloat("vscale", uvscale);
+        t.uoffset = (float) p.getFloat("uoffset", 0.0f);
+        t.voffset = (float) p.getFloat("voffset", 0.0f);
+        float avg[4];
+        pgRGB(tex->getAverage(), avg);
+        for (int a = 0; a < 3; ++a) t.average[a] = std::max(avg[a], 0.0f);
+        texIndex[tex.get()] = (uint32_t) f.textures.size();
+        f.textures.push_back(t);
+        f.texels.push_back(rgb);
+    }
+    pg_texture_binding b;
+    b.material = material;
+    b.texture = texIndex[tex.get()];
+    f.bindings.push_back(b);
+}
+
 inline void GuidedGPUIntegrator::flattenEnvironment(const Scene *scene, Flattened &f) const {
     const Emitter *env = scene->getEnvironmentEmitter();
     if (!env) return;
@@ -614,6 +699,7 @@ inline GuidedGPUIntegrator::Flattened GuidedGPUIntegrator::flatten(const Scene *
     Flattened f;
     memset(&f.desc, 0, sizeof(f.desc));
     std::map<const BSDF *, uint32_t> matIndex;
+    std::map<const Texture *, uint32_t> texIndex;
     std::map<const Medium *, AABB> mediumBounds;             // AABB of each medium's boundary shapes
     for (const Shape *shape : scene->getShapes())
         for (const Medium *m : {shape->getInteriorMedium(), shape->getExteriorMedium()})
@@ -634,6 +720,7 @@ inline GuidedGPUIntegrator::Flattened GuidedGPUIntegrator::flatten(const Scene *
         if (!matIndex.count(bsdf)) {
             matIndex[bsdf] = (uint32_t) f.mats.size();
             f.mats.push_back(material(bsdf));
+            flattenTexture(bsdf, matIndex[bsdf], texIndex, f);
         }
         pg_shape s;
         s.tri_begin = (uint32_t) (f.idx.size() / 3);
@@ -652,7 +739,9 @@ inline GuidedGPUIntegrator::Flattened GuidedGPUIntegrator::flatten(const Scene *
         }
         const Point *P = mesh->getVertexPositions();         // trimesh.h:122-141, world space
         const Normal *N = mesh->getVertexNormals();
-        const Triangle *T = mesh->getTriangles();
+        const Point2 *UV = mesh->getVertexTexcoords();       // trimesh.h:151; NULL: zeros (Intersection::uv = (b1, b2)
+        const Triangle *T = mesh->getTriangles();            // only when no mesh of the scene has texcoords)
+        if (UV) f.hasUV = true;
         if (N) {                                             // shared vertices with shading normals
             const uint32_t base = (uint32_t) (f.pos.size() / 3);
             for (size_t v = 0; v < mesh->getVertexCount(); ++v)
@@ -660,6 +749,8 @@ inline GuidedGPUIntegrator::Flattened GuidedGPUIntegrator::flatten(const Scene *
                     f.pos.push_back((float) P[v][a]);
                     f.nrm.push_back((float) N[v][a]);
                 }
+            for (size_t v = 0; v < mesh->getVertexCount(); ++v)
+                for (int a = 0; a < 2; ++a) f.uv.push_back(UV ? (float) UV[v][a] : 0.0f);
             for (size_t t = 0; t < mesh->getTriangleCount(); ++t)
                 for (int k = 0; k < 3; ++k) f.idx.push_back(base + T[t].idx[k]);
         } else {                                             // no normals: Mitsuba shades with the face normal
@@ -672,6 +763,7 @@ inline GuidedGPUIntegrator::Flattened GuidedGPUIntegrator::flatten(const Scene *
                         f.pos.push_back((float) q[ax]);
                         f.nrm.push_back((float) n[ax]);
                     }
+                    for (int a = 0; a < 2; ++a) f.uv.push_back(UV ? (float) UV[T[t].idx[k]][a] : 0.0f);
                     f.idx.push_back((uint32_t) (f.pos.size() / 3 - 1));
                 }
             }
