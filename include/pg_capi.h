@@ -452,6 +452,34 @@ pg_status pg_set_textures(void *ctx, const pg_texture *textures, uint32_t n_text
  * the texcoords of the last pg_set_textures, else the barycentrics. */
 pg_status pg_texture_query(void *ctx, const pg_texture *texture, const float *uv, uint64_t n, float *out);
 pg_status pg_hit_uvs(void *ctx, const float *rays, uint64_t n, float *out);
+/* ---- thin-lens sensor: depth of field in both integrators ---------------------------------------------------------
+ * New entry points; pg_config, pg_stats, pg_scene_desc, pg_camera and PG_ABI_VERSION are unchanged.  The camera of
+ * pg_scene_desc is a pinhole (PerspectiveCamera::sampleRay, perspective.cpp:271-298); pg_set_lens puts the thin lens
+ * of ThinLens::sampleRay (thinlens.cpp:293-322) in front of it.  With nearP = ((1 - 2 sx) tan_half,
+ * (1 - 2 sy) / aspect tan_half, 1) the pinhole's local near-plane point of the sample (float32, no contraction):
+ *   (a0, a1)  = draw (sample, dimension 0x40000000) of the pixel's counter stream.  The reference draws the aperture
+ *               sample right after the pixel sample (progressiveintegrator.cpp:263-264); here it has a dimension no
+ *               other draw uses (surface path: 0 and 8 depth + slot; volumetric path: 1, 2, ...; the transmittance
+ *               walks use other keys), so every later draw of a path is the same with the lens on or off.
+ *   tmp       = squareToUniformDiskConcentric(a0, a1) * aperture_radius   (warp.cpp:81-102)
+ *   focusP    = nearP * focus_distance                                    (nearP.z = 1)
+ *   dl        = normalize(focusP - (tmp.x, tmp.y, 0)),  invZ = 1 / dl.z
+ *   origin    = camera origin + left tmp.x + up tmp.y
+ *   direction = left dl.x + up dl.y + dir dl.z,  tmin = near_clip invZ,  tmax = far_clip invZ
+ * aperture_radius == 0 turns the lens off (focus_distance is then ignored and read back as 0): the pinhole kernels
+ * run and every result is bit for bit that of a context on which the call was never made.  This deviates from the
+ * reference, which turns a zero radius into Epsilon (thinlens.cpp:134-137).  PG_ERR_INVALID, with the state left as
+ * it was: a negative or non-finite radius, a non-finite focus distance, a focus distance <= 0 with a radius > 0.
+ * Valid for both integrators and at any time; it takes effect at the next pass.  It does not touch the film, the
+ * SD-tree or the shadow-blocker list: the caller resets the film as after any camera change (the trained tree stays
+ * valid, the lens only moves the first hits).  pg_upload_scene turns the lens off, its camera being a pinhole. */
+pg_status pg_set_lens(void *ctx, float aperture_radius, float focus_distance);
+pg_status pg_get_lens(void *ctx, float *aperture_radius, float *focus_distance); /* either may be NULL */
+/* Unit entry point (parity tests): the camera rays the integrators generate, by the device function they call, for
+ * n (global pixel = y * width + x, sample index) pairs under the context's camera, seed and lens.
+ * o_tmin: n x 4 floats (origin, tmin); d_tmax: n x 4 floats (direction, tmax). */
+pg_status pg_camera_rays(void *ctx, const uint32_t *pixels, const uint32_t *samples, uint32_t n, float *o_tmin,
+                         float *d_tmax);
 pg_status pg_get_stats(void *ctx, pg_stats *stats);
 /* Path integrator: segments (counted in pg_stats.segments, not in escaped) whose hit was culled by the
  * closest-hit kernels since create: the ray's next vertex had already lost its Russian roulette, or was past the

@@ -107,6 +107,66 @@ PGD f3 squareToCosineHemisphere(float sx, float sy) {
     return mk(px, py, z);
 }
 PGD float cosineHemispherePdf(f3 d) { return kInvPi * d.z; }
+// squareToUniformDiskConcentric (warp.cpp:81-102): the concentric map squareToCosineHemisphere starts with
+PGD void squareToUniformDiskConcentric(float sx, float sy, float &px, float &py) {
+    float r1 = 2.0f * sx - 1.0f, r2 = 2.0f * sy - 1.0f, phi, r;
+    if (r1 == 0 && r2 == 0) {
+        r = phi = 0;
+    } else if (r1 * r1 > r2 * r2) {
+        r = r1;
+        phi = (kPi / 4.0f) * (r2 / r1);
+    } else {
+        r = r2;
+        phi = (kPi / 2.0f) - (r1 / r2) * (kPi / 4.0f);
+    }
+    float sp, cp;
+    sincosf(phi, &sp, &cp);
+    px = r * cp;
+    py = r * sp;
+}
+
+// ---- camera rays (DESIGN.md "RNG" / "Thin lens").  The one definition k_camera, volCamera (k_vcam, k_volpath)
+// and k_camera_rays share.  LENS false: PerspectiveCamera::sampleRay (perspective.cpp:271-298), the arithmetic
+// the two integrators had inline.  LENS true: ThinLens::sampleRay (thinlens.cpp:293-322) on the same local nearP
+// (its z is 1, so m_focusDistance / nearP.z is the focus distance).  The aperture sample is its own dimension of
+// the path's counter stream, far from the ones the integrators count through (surface: 8 depth + slot, volumetric:
+// 1, 2, ...), so every later draw of a path is the same with the lens on or off.
+constexpr uint32_t PG_DIM_APERTURE = 0x40000000u;
+template <bool LENS>
+PGD void cameraRay(const GParams &g, uint32_t pix, uint32_t key, uint32_t sample, f3 &o, f3 &wd, float &tmin,
+                   float &tmax) {
+    float jx, jy;
+    rng2(key, sample, 0, jx, jy);
+    const float px = (float)(pix % g.width) + jx, py = (float)(pix / g.width) + jy;
+    const float sx = px / (float)g.width, sy = py / (float)g.height;
+    const f3 nearP = mk((1.0f - 2.0f * sx) * g.tan_half, (1.0f - 2.0f * sy) / g.aspect * g.tan_half, 1.0f);
+    f3 d;
+    float ax = 0.0f, ay = 0.0f;  // the aperture point, local
+    if constexpr (LENS) {
+#pragma clang fp contract(off)
+        float a0, a1;
+        rng2(key, sample, PG_DIM_APERTURE, a0, a1);
+        squareToUniformDiskConcentric(a0, a1, ax, ay);
+        ax = ax * g.lens_radius;
+        ay = ay * g.lens_radius;
+        const f3 focusP = nearP * g.focus_dist;
+        d = normalize(focusP - mk(ax, ay, 0.0f));
+    } else {
+        d = normalize(nearP);
+    }
+    const float invZ = 1.0f / d.z;
+    const f3 left = mk(g.cam_left[0], g.cam_left[1], g.cam_left[2]);
+    const f3 up = mk(g.cam_up[0], g.cam_up[1], g.cam_up[2]);
+    const f3 dir = mk(g.cam_dir[0], g.cam_dir[1], g.cam_dir[2]);
+    wd = left * d.x + up * d.y + dir * d.z;
+    o = mk(g.cam_o[0], g.cam_o[1], g.cam_o[2]);
+    if constexpr (LENS) {
+#pragma clang fp contract(off)
+        o = o + left * ax + up * ay;
+    }
+    tmin = g.near_clip * invZ;
+    tmax = g.far_clip * invZ;
+}
 
 // ---- Fresnel (src/libcore/util.cpp:653-683, 741-763)
 PGD float fresnelDielectricExt(float cosThetaI_, float &cosThetaT_, float eta) {

@@ -1025,6 +1025,57 @@ pg_status pg_set_rfilter(void *ctx, float radius, const float *values) {
     return c->has_scene ? setupFiltered(c) : PG_OK;
 }
 
+// ---- thin lens (pg_capi.h pg_set_lens) ------------------------------------------------------------------------------
+// The lens lives in the context's GParams, which every pass copies: pg_upload_scene's memset turns it off.
+pg_status pg_set_lens(void *ctx, float aperture_radius, float focus_distance) {
+    Ctx *c = (Ctx *)ctx;
+    if (!c) return fail(nullptr, PG_ERR_INVALID, "pg_set_lens: null context");
+    if (!std::isfinite(aperture_radius) || aperture_radius < 0)
+        return fail(c, PG_ERR_INVALID, "pg_set_lens: the aperture radius must be finite and >= 0");
+    if (!std::isfinite(focus_distance)) return fail(c, PG_ERR_INVALID, "pg_set_lens: non-finite focus distance");
+    if (aperture_radius > 0 && !(focus_distance > 0))
+        return fail(c, PG_ERR_INVALID, "pg_set_lens: the focus distance of a lens must be > 0");
+    c->g.lens_radius = aperture_radius;
+    c->g.focus_dist = aperture_radius > 0 ? focus_distance : 0.0f;
+    return PG_OK;
+}
+
+pg_status pg_get_lens(void *ctx, float *aperture_radius, float *focus_distance) {
+    Ctx *c = (Ctx *)ctx;
+    if (!c) return fail(nullptr, PG_ERR_INVALID, "pg_get_lens: null context");
+    if (aperture_radius) *aperture_radius = c->g.lens_radius;
+    if (focus_distance) *focus_distance = c->g.focus_dist;
+    return PG_OK;
+}
+
+pg_status pg_camera_rays(void *ctx, const uint32_t *pixels, const uint32_t *samples, uint32_t n, float *o_tmin,
+                         float *d_tmax) {
+    Ctx *c = (Ctx *)ctx;
+    if (!c || (n && (!pixels || !samples || !o_tmin || !d_tmax)))
+        return fail(c, PG_ERR_INVALID, "pg_camera_rays: null argument");
+    if (!c->has_scene) return fail(c, PG_ERR_STATE, "pg_camera_rays: no scene");
+    const uint64_t npix = (uint64_t)c->g.width * c->g.height;
+    for (uint32_t i = 0; i < n; ++i)
+        if (pixels[i] >= npix) return fail(c, PG_ERR_INVALID, "pg_camera_rays: pixel outside the film");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    if (!n) return PG_OK;
+    GParams g = c->g;
+    g.seed = c->cfg.seed;  // as the passes set it
+    DevBuf p, s, o, d;
+    HIPC(c, p.alloc((size_t)n * 4));
+    HIPC(c, s.alloc((size_t)n * 4));
+    HIPC(c, o.alloc((size_t)n * 16));
+    HIPC(c, d.alloc((size_t)n * 16));
+    HIPC(c, hipMemcpyAsync(p.p, pixels, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipMemcpyAsync(s.p, samples, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    pg_launch_camera_rays(c->stream, g, p.as<uint32_t>(), s.as<uint32_t>(), n, o.as<float>(), d.as<float>());
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipMemcpyAsync(o_tmin, o.p, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(d_tmax, d.p, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    return PG_OK;
+}
+
 // ---- textures (pg_capi.h pg_set_textures) ---------------------------------------------------------------------------
 namespace {
 // pg_texture -> GTex (texels left null) with its validation; err: what is wrong with it

@@ -173,6 +173,10 @@ inline uint32_t pg_camera_bound(bool banded, uint32_t npix, uint32_t nlayers) {
 
 void pg_launch_camera(hipStream_t s, const GParams &g, const PathDev &p, const uint32_t *local_pixels,
                       uint32_t pix_begin, uint32_t npix, uint32_t nlayers, uint32_t sample_base, Queue q, bool banded);
+// unit-level camera rays (pg_camera_rays): the device function k_camera and the volumetric camera stages call, for
+// n (global pixel, sample) pairs; o_tmin, d_tmax: n x 4 floats each
+void pg_launch_camera_rays(hipStream_t s, const GParams &g, const uint32_t *pixels, const uint32_t *samples, uint32_t n,
+                           float *o_tmin, float *d_tmax);
 // closest hit for the live queue, partitioned by the hit's material class: class c < PG_NUM_CLASSES
 // goes to class_queues[c] (shard s -> shard s); escaped paths are only counted, in
 // class_queues[PG_NUM_CLASSES].counts.  max_shard: upper bound of the largest shard count (sizes

@@ -33,7 +33,9 @@
 #endif
 
 // =============================================================================================
-// camera rays: PerspectiveCamera::sampleRay (perspective.cpp:271-298) for (pixel, sample) slots
+// camera rays (cameraRay, pg_device.h) for (pixel, sample) slots.  LENS: a thin lens is set (pg_set_lens); the
+// pinhole launches k_camera<false>, the kernel as it was
+template <bool LENS>
 __global__ __launch_bounds__(256) void k_camera(GParams g, PathDev p, const uint32_t *__restrict__ local_pixels,
                                                 uint32_t pix_begin, uint32_t npix, uint32_t nlayers,
                                                 uint32_t sample_base, Queue q, bool banded) {
@@ -44,20 +46,11 @@ __global__ __launch_bounds__(256) void k_camera(GParams g, PathDev p, const uint
     uint32_t layer = slot / npix, lp = slot - layer * npix;
     uint32_t pix = local_pixels[pix_begin + lp];
     uint32_t sample = sample_base + layer;
-    uint32_t key = rngKey(pix, g.seed);
-    float jx, jy;
-    rng2(key, sample, 0, jx, jy);
-    float px = (float)(pix % g.width) + jx, py = (float)(pix / g.width) + jy;
-    float sx = px / (float)g.width, sy = py / (float)g.height;
-    f3 nearP = mk((1.0f - 2.0f * sx) * g.tan_half, (1.0f - 2.0f * sy) / g.aspect * g.tan_half, 1.0f);
-    f3 d = normalize(nearP);
-    float invZ = 1.0f / d.z;
-    f3 left = mk(g.cam_left[0], g.cam_left[1], g.cam_left[2]);
-    f3 up = mk(g.cam_up[0], g.cam_up[1], g.cam_up[2]);
-    f3 dir = mk(g.cam_dir[0], g.cam_dir[1], g.cam_dir[2]);
-    f3 wd = left * d.x + up * d.y + dir * d.z;
-    stS(&p.ray_o[slot], make_float4(g.cam_o[0], g.cam_o[1], g.cam_o[2], g.near_clip * invZ));
-    stS(&p.ray_d[slot], f4(wd, g.far_clip * invZ));
+    f3 o, wd;
+    float tmin, tmax;
+    cameraRay<LENS>(g, pix, rngKey(pix, g.seed), sample, o, wd, tmin, tmax);
+    stS(&p.ray_o[slot], f4(o, tmin));
+    stS(&p.ray_d[slot], f4(wd, tmax));
     // throughput (1, eta 1) is implied by depth 1: the first bounce's readers (shadeOne, envEscapeRadiance) do not
     // load it.  ray_d.w is the far clip along the ray; a bounce ray keeps woPdf there (pg_layout.h "Path state").
     // L = 0 is stored: a camera ray that escapes is
@@ -1816,8 +1809,35 @@ void pg_launch_camera(hipStream_t s, const GParams &g, const PathDev &p, const u
                       uint32_t pix_begin, uint32_t npix, uint32_t nlayers, uint32_t sample_base, Queue q, bool banded) {
     uint64_t n = (uint64_t)npix * nlayers;
     if (!n) return;
-    hipLaunchKernelGGL(k_camera, dim3(blocks(n, 256)), dim3(256), 0, s, g, p, local_pixels, pix_begin, npix, nlayers,
-                       sample_base, q, pg_camera_banded(banded, npix));
+    if (g.lens_radius > 0)
+        hipLaunchKernelGGL(k_camera<true>, dim3(blocks(n, 256)), dim3(256), 0, s, g, p, local_pixels, pix_begin, npix,
+                           nlayers, sample_base, q, pg_camera_banded(banded, npix));
+    else
+        hipLaunchKernelGGL(k_camera<false>, dim3(blocks(n, 256)), dim3(256), 0, s, g, p, local_pixels, pix_begin, npix,
+                           nlayers, sample_base, q, pg_camera_banded(banded, npix));
+}
+// pg_camera_rays: cameraRay for given (global pixel, sample) pairs; out: (o, tmin) and (d, tmax) per pair
+template <bool LENS>
+__global__ __launch_bounds__(256) void k_camera_rays(GParams g, const uint32_t *__restrict__ pixels,
+                                                     const uint32_t *__restrict__ samples, uint32_t n,
+                                                     float4 *__restrict__ o_tmin, float4 *__restrict__ d_tmax) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t pix = pixels[i];
+    f3 o, wd;
+    float tmin, tmax;
+    cameraRay<LENS>(g, pix, rngKey(pix, g.seed), samples[i], o, wd, tmin, tmax);
+    o_tmin[i] = f4(o, tmin);
+    d_tmax[i] = f4(wd, tmax);
+}
+void pg_launch_camera_rays(hipStream_t s, const GParams &g, const uint32_t *pixels, const uint32_t *samples, uint32_t n,
+                           float *o_tmin, float *d_tmax) {
+    if (!n) return;
+    float4 *o = reinterpret_cast<float4 *>(o_tmin), *d = reinterpret_cast<float4 *>(d_tmax);
+    if (g.lens_radius > 0)
+        hipLaunchKernelGGL(k_camera_rays<true>, dim3(blocks(n, 256)), dim3(256), 0, s, g, pixels, samples, n, o, d);
+    else
+        hipLaunchKernelGGL(k_camera_rays<false>, dim3(blocks(n, 256)), dim3(256), 0, s, g, pixels, samples, n, o, d);
 }
 // grid of a sharded launch: PG_QSHARDS x rows (rows capped for persistent grid-stride kernels)
 static inline dim3 shardGrid(uint32_t max_shard, uint32_t block, uint32_t max_rows) {

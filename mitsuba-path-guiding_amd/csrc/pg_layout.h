@@ -543,4 +543,7 @@ struct GParams {
     int32_t glossy_prior;    // pg_config.glossy_prior
     int32_t path_cull;       // 1: shadeOne decides PF_DOOMED one bounce early and the tracer culls (PG_NO_PATH_CULL: 0)
     int32_t doom_probe;      // 1: a doomed ray that misses every emitter box is probed, not traced (PG_NO_DOOM_PROBE: 0)
+    // thin lens (pg_set_lens): world-space aperture radius, 0 = pinhole (the lens kernels are not launched), and
+    // the distance of the focal plane along the viewing direction
+    float lens_radius, focus_dist;
 };

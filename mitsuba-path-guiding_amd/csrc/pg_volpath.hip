@@ -1006,8 +1006,9 @@ __device__ __forceinline__ bool volStepResolved(const GParams &g, const SceneDev
     return alive;
 }
 
-// the camera ray of work item `item` (PerspectiveCamera::sampleRay, perspective.cpp:271-298) and its
+// the camera ray of work item `item` (cameraRay, pg_device.h; LENS: a thin lens is set) and its
 // first hit: a new path state
+template <bool LENS>
 __device__ __forceinline__ void volCamera(const GParams &g, const SceneDev &sc, const VolDev &v,
                                           const uint32_t *__restrict__ local_pixels, uint32_t pix_begin, uint32_t npix,
                                           uint32_t sample_base, uint32_t item, VPath &P, VRng &rng, const TStack &stk,
@@ -1015,19 +1016,11 @@ __device__ __forceinline__ void volCamera(const GParams &g, const SceneDev &sc, 
     const uint32_t layer = item / npix, lp = item - layer * npix;
     const uint32_t pix = local_pixels[pix_begin + lp];
     rng = VRng{rngKey(pix, g.seed), sample_base + layer, 1, 0};
-    float jx, jy;
-    rng2(rng.key, rng.sample, 0, jx, jy);
-    const float px = (float)(pix % g.width) + jx, py = (float)(pix / g.width) + jy;
-    const float sx = px / (float)g.width, sy = py / (float)g.height;
-    const f3 nearP = mk((1.0f - 2.0f * sx) * g.tan_half, (1.0f - 2.0f * sy) / g.aspect * g.tan_half, 1.0f);
-    const f3 dl = normalize(nearP);
-    const float invZ = 1.0f / dl.z;
-    P.o = mk(g.cam_o[0], g.cam_o[1], g.cam_o[2]);
-    P.d = mk(g.cam_left[0], g.cam_left[1], g.cam_left[2]) * dl.x +
-          mk(g.cam_up[0], g.cam_up[1], g.cam_up[2]) * dl.y + mk(g.cam_dir[0], g.cam_dir[1], g.cam_dir[2]) * dl.z;
+    float tmin, tmax;
+    cameraRay<LENS>(g, pix, rng.key, rng.sample, P.o, P.d, tmin, tmax);
     float t, u, w;
     uint32_t tri;
-    const bool hit = closestHit(sc, P.o, P.d, g.near_clip * invZ, g.far_clip * invZ, t, tri, u, w, stk);
+    const bool hit = closestHit(sc, P.o, P.d, tmin, tmax, t, tri, u, w, stk);
     segs++;
     P.its = ItsRef{hit, hit ? t : __int_as_float(0x7f800000), u, w, tri};
     P.T = mk1(1.f);
@@ -1192,7 +1185,7 @@ __device__ __forceinline__ void flightAppend(bool pred, uint32_t slot, uint16_t 
 // (k_vvertex: no wave runs both branches), each path in its slot with its random stream carried in
 // VolWave, so films and trees are bit-identical to k_volpath's (which runs the same volFlight /
 // volMedium / volSurface per lane).  The last few paths finish one thread each (k_vtail).
-template <bool GUIDED>
+template <bool GUIDED, bool LENS>
 __global__ __launch_bounds__(TRACE_BLOCK) void k_vcam(GParams g, SceneDev sc, VolDev v, VolWave w,
                                                       const uint32_t *__restrict__ local_pixels, uint32_t pix_begin,
                                                       uint32_t npix, uint32_t nlayers, uint32_t sample_base, Queue qf,
@@ -1208,7 +1201,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) void k_vcam(GParams g, SceneDev sc, Vo
         if (slot < n) {
             VPath P;
             VRng rng;
-            volCamera(g, sc, v, local_pixels, pix_begin, npix, sample_base, slot, P, rng, stk, segs);
+            volCamera<LENS>(g, sc, v, local_pixels, pix_begin, npix, sample_base, slot, P, rng, stk, segs);
             if (!volDepthOk(g, P)) {
                 volEnd(v, slot, P, rng, lookups);
             } else {
@@ -1463,12 +1456,15 @@ void pg_launch_vol_camera(hipStream_t s, const GParams &g, const SceneDev &sc, c
     if (!n) return;
     const uint64_t want = (n + TRACE_BLOCK - 1) / TRACE_BLOCK;
     const dim3 grid((uint32_t)(want < TRACE_MAX_BLOCKS ? want : TRACE_MAX_BLOCKS));  // the overflow ring's size
-    if (g.guiding)
-        hipLaunchKernelGGL(k_vcam<true>, grid, dim3(TRACE_BLOCK), 0, s, g, sc, v, w, local_pixels, pix_begin, npix,
-                           nlayers, sample_base, flight, surf, dsurf);
-    else
-        hipLaunchKernelGGL(k_vcam<false>, grid, dim3(TRACE_BLOCK), 0, s, g, sc, v, w, local_pixels, pix_begin, npix,
-                           nlayers, sample_base, flight, surf, dsurf);
+#define PG_VC(G, L)                                                                                            \
+    hipLaunchKernelGGL((k_vcam<G, L>), grid, dim3(TRACE_BLOCK), 0, s, g, sc, v, w, local_pixels, pix_begin, npix, \
+                       nlayers, sample_base, flight, surf, dsurf)
+    if (g.lens_radius > 0) {  // a thin lens (pg_set_lens); off: the kernels as they were
+        if (g.guiding) PG_VC(true, true); else PG_VC(false, true);
+    } else {
+        if (g.guiding) PG_VC(true, false); else PG_VC(false, false);
+    }
+#undef PG_VC
 }
 void pg_launch_vol_flight(hipStream_t s, const GParams &g, const SceneDev &sc, const VolDev &v, const SDDev &sd,
                           const VolWave &w, Queue flight, uint32_t max_flight, Queue med, Queue surf, Queue dsurf) {
@@ -1547,7 +1543,7 @@ void pg_launch_vol_tail(hipStream_t s, const GParams &g, const SceneDev &sc, con
 namespace {
 }  // namespace
 
-template <bool GUIDED>
+template <bool GUIDED, bool LENS>
 __global__ __launch_bounds__(VOL_BLOCK, PG_VOL_WAVES) void k_volpath(GParams g, SceneDev sc, VolDev v, SDDev sd,
                                                        const uint32_t *__restrict__ local_pixels, uint32_t pix_begin,
                                                        uint32_t npix, uint32_t nlayers, uint32_t sample_base) {
@@ -1575,7 +1571,7 @@ __global__ __launch_bounds__(VOL_BLOCK, PG_VOL_WAVES) void k_volpath(GParams g, 
                 if (item >= nitems) {
                     done = true;
                 } else {
-                    volCamera(g, sc, v, local_pixels, pix_begin, npix, sample_base, item, P, rng, stk, segs);
+                    volCamera<LENS>(g, sc, v, local_pixels, pix_begin, npix, sample_base, item, P, rng, stk, segs);
                     alive = true;
                 }
             }
@@ -1710,10 +1706,13 @@ void pg_launch_volpath(hipStream_t s, const GParams &g, const SceneDev &sc, cons
     (void)hipMemsetAsync(v.next, 0, sizeof(uint32_t), s);
     const uint64_t want = (n + VOL_BLOCK - 1) / VOL_BLOCK;
     const uint32_t grid = (uint32_t)(want < TRACE_MAX_BLOCKS ? want : TRACE_MAX_BLOCKS);
-    if (g.guiding)
-        hipLaunchKernelGGL(k_volpath<true>, dim3(grid), dim3(VOL_BLOCK), 0, s, g, sc, v, sd, local_pixels, pix_begin,
-                           npix, nlayers, sample_base);
-    else
-        hipLaunchKernelGGL(k_volpath<false>, dim3(grid), dim3(VOL_BLOCK), 0, s, g, sc, v, sd, local_pixels, pix_begin,
-                           npix, nlayers, sample_base);
+#define PG_VP(G, L)                                                                                              \
+    hipLaunchKernelGGL((k_volpath<G, L>), dim3(grid), dim3(VOL_BLOCK), 0, s, g, sc, v, sd, local_pixels, pix_begin, \
+                       npix, nlayers, sample_base)
+    if (g.lens_radius > 0) {  // a thin lens (pg_set_lens); off: the kernels as they were
+        if (g.guiding) PG_VP(true, true); else PG_VP(false, true);
+    } else {
+        if (g.guiding) PG_VP(true, false); else PG_VP(false, false);
+    }
+#undef PG_VP
 }

@@ -16,7 +16,7 @@
 
 Properties use the reference's XML names (maxDepth, rrDepth, strictNormals, hideEmitters, useNee,
 samplesPerProgression, maxComponentValue; guiding: trainingIterations, sTreeThreshold,
-dTreeThreshold, bsdfSamplingFraction, distanceGuiding).  Errors raise RuntimeError with pg_last_error(), like
+dTreeThreshold, bsdfSamplingFraction, distanceGuiding; sensor override: apertureRadius, focusDistance).  Errors raise RuntimeError with pg_last_error(), like
 Log(EError, ...) throws in Mitsuba.  There is no CPU fallback: without libpgamd.so or a gfx950
 device every entry point raises.
 """
@@ -122,6 +122,31 @@ class Device:
         self._chk(self.lib.pg_upload_scene(self.h, C.byref(scene.desc())))
         if getattr(scene, "texture_bindings", None):  # pg_upload_scene cleared any textures of an earlier scene
             self.set_textures(scene.textures, scene.texture_bindings, scene.texcoords)
+        if getattr(scene, "lens", None):  # pg_upload_scene turned the lens off: its camera is a pinhole
+            self.set_lens(*scene.lens)
+
+    def set_lens(self, aperture_radius, focus_distance=0.0):
+        """pg_set_lens: a thin lens of world-space radius `aperture_radius` focused at `focus_distance` along the
+        viewing direction; radius 0 turns it off.  Takes effect at the next pass; reset the film after a change."""
+        self._chk(self.lib.pg_set_lens(self.h, float(aperture_radius), float(focus_distance)))
+
+    def get_lens(self):
+        """pg_get_lens: (aperture radius, focus distance); (0, 0) for the pinhole."""
+        r, f = C.c_float(), C.c_float()
+        self._chk(self.lib.pg_get_lens(self.h, C.byref(r), C.byref(f)))
+        return r.value, f.value
+
+    def camera_rays(self, pixels, samples):
+        """pg_camera_rays: the integrators' camera rays of (global pixel, sample index) pairs under the context's
+        camera, seed and lens: ((n, 4) origin + tmin, (n, 4) direction + tmax)."""
+        pixels = np.ascontiguousarray(pixels, np.uint32).ravel()
+        samples = np.ascontiguousarray(samples, np.uint32).ravel()
+        if pixels.shape != samples.shape:
+            raise ValueError("camera_rays: one sample index per pixel")
+        o = np.zeros((len(pixels), 4), np.float32)
+        d = np.zeros((len(pixels), 4), np.float32)
+        self._chk(self.lib.pg_camera_rays(self.h, _p(pixels), _p(samples), len(pixels), _p(o), _p(d)))
+        return o, d
 
     def set_textures(self, textures, bindings, texcoords=None):
         """pg_set_textures: pg_texture records (scenes.make_texture), (material, texture) pairs and per-vertex
@@ -440,6 +465,15 @@ class ProgressivePathTracer:
         if self.rfilter is not None and self.rfilter not in ("scene",) + tuple(_RFILTERS):
             raise ValueError(f"rfilter must be box, tent, gaussian or scene, not {self.rfilter!r}")
         self.stddev = float(props.get("stddev", 0.5))
+        # sensor override by Mitsuba's property names (thinlens.cpp:132, sensor.cpp:162): a thin lens in front of the
+        # scene's camera, whatever lens the scene carries; apertureRadius 0 forces the pinhole
+        self.lens = None
+        if "apertureRadius" in props:
+            if "focusDistance" not in props and float(props["apertureRadius"]) > 0:
+                raise ValueError("apertureRadius needs focusDistance")
+            self.lens = (float(props["apertureRadius"]), float(props.get("focusDistance", 0.0)))
+        elif "focusDistance" in props:
+            raise ValueError("focusDistance needs apertureRadius")
         self.filtered = None
         self.developed = None
         self.dev = None
@@ -455,6 +489,8 @@ class ProgressivePathTracer:
             self.dev.set_rfilter(name, stddev)
         elif self.rfilter is not None:
             self.dev.set_rfilter(self.rfilter, self.stddev)
+        if self.lens is not None:
+            self.dev.set_lens(*self.lens)
         self.progression = 0
         self.sample_offset = 0
         return True
@@ -535,6 +571,10 @@ class ProgressivePathTracer:
             done += progs * self.spp_per_progression
             per_prog = (time.perf_counter() - t) / progs
         return done
+
+    def camera_rays(self, pixels, samples):
+        """The camera rays of (global pixel, sample index) pairs (Device.camera_rays), after preprocess()."""
+        return self.dev.camera_rays(pixels, samples)
 
     def denoiser_features(self):
         """Per-pixel means of the first-hit albedo and normal (what Denoiser::add averages,

@@ -12,6 +12,9 @@ adapter's flatten() produces from Scene::getShapes()/getBSDFs() (INTEGRATION.md)
   integrator        any type: (type, properties) returned for the caller (ProgressivePathTracer props)
   sensor            perspective: fov, fovAxis (x, y, diagonal, smaller, larger), nearClip, farClip,
                     toWorld (a mirrored camera, e.g. <scale x="-1"/>, sets Scene.mirror_x);
+                    thinlens: the same plus apertureRadius (required, thinlens.cpp:132) and focusDistance
+                    (default: farClip, sensor.cpp:162), recorded as Scene.lens; apertureRadius 0 is the pinhole
+                    (the reference makes it Epsilon, thinlens.cpp:134-137);
                     sampler sampleCount; film width / height and rfilter (box, tent, gaussian: recorded as Scene.rfilter)
   bsdf              diffuse, conductor, roughconductor (material Cu / Al / Au / none, or eta + k),
                     dielectric, roughdielectric, plastic, roughplastic (intIOR / extIOR by value or
@@ -533,9 +536,12 @@ class _Loader:
 
     def sensor(self, el):
         typ = self.attr(el, "type")
-        if typ != "perspective":
-            raise NotImplementedError(f"<sensor type=\"{typ}\"> (perspective only)")
+        if typ not in ("perspective", "thinlens"):
+            raise NotImplementedError(f"<sensor type=\"{typ}\"> (perspective and thinlens only)")
         P = self.props(el)
+        for k in ("shutterOpen", "shutterClose"):
+            if typ == "thinlens" and float(P.get(k, 0.0)) != 0.0:
+                raise NotImplementedError(f"<sensor type=\"thinlens\">: {k} (no motion blur)")
         W, H = 768, 576  # hdrfilm defaults (src/films/hdrfilm.cpp)
         for c in el:
             if c.tag == "film":
@@ -573,6 +579,14 @@ class _Loader:
         self.sc.mirror_x = bool(np.dot(left, left_m) < 0)
         self.sc.set_camera(tuple(o), tuple(o + d / np.linalg.norm(d)), tuple(up / np.linalg.norm(up)), fov_x, W, H,
                            near=float(P.get("nearClip", 1e-2)), far=float(P.get("farClip", 1e4)))
+        if typ == "thinlens":
+            if "apertureRadius" not in P:  # Properties::getFloat without a default throws (thinlens.cpp:132)
+                raise ValueError("<sensor type=\"thinlens\">: the apertureRadius property is required")
+            if not np.allclose(np.linalg.norm(M[:3, :3], axis=0), 1.0, atol=1e-4):
+                raise ValueError("<sensor type=\"thinlens\">: scale factors in toWorld are not allowed "
+                                 "(thinlens.cpp:140-142)")
+            # ProjectiveCamera: focusDistance defaults to the far clip (sensor.cpp:160-162)
+            self.sc.set_lens(float(P["apertureRadius"]), float(P.get("focusDistance", P.get("farClip", 1e4))))
 
     def run(self, root):
         if root.tag != "scene":
@@ -1054,8 +1068,8 @@ def _bsdf_xml(m, tex=None):
 
 def save(scene, path, spp=64, integrator="path"):
     """Write `scene` as a Mitsuba 0.5 scene: one OBJ per shape (positions, normals), inline BSDFs,
-    area emitters, the perspective sensor (lookat + fov along x), a box-filtered hdrfilm, and the
-    environment map as a PFM.  load(path) reads it back to the same arrays."""
+    area emitters, the perspective sensor (lookat + fov along x; thinlens with apertureRadius and focusDistance
+    when the scene has a lens), a box-filtered hdrfilm, and the environment map as a PFM.  load(path) reads it back to the same arrays."""
     d = os.path.dirname(os.path.abspath(path))
     stem = os.path.splitext(os.path.basename(path))[0]
     os.makedirs(d, exist_ok=True)
@@ -1066,7 +1080,10 @@ def save(scene, path, spp=64, integrator="path"):
     cam = sc.camera
     v3 = lambda a: f"{a[0]!r}, {a[1]!r}, {a[2]!r}"
     f32l = lambda a: [float(np.float32(x)) for x in a]
-    out.append(f'<sensor type="perspective"><float name="fov" value="{float(np.float32(cam.fov_x_deg))!r}"/>'
+    lens = getattr(sc, "lens", None)
+    lens_xml = "" if not lens else (f'<float name="apertureRadius" value="{float(np.float32(lens[0]))!r}"/>'
+                                    f'<float name="focusDistance" value="{float(np.float32(lens[1]))!r}"/>')
+    out.append(f'<sensor type="{"thinlens" if lens else "perspective"}">{lens_xml}<float name="fov" value="{float(np.float32(cam.fov_x_deg))!r}"/>'
                f'<string name="fovAxis" value="x"/><float name="nearClip" value="{float(np.float32(cam.near_clip))!r}"/>'
                f'<float name="farClip" value="{float(np.float32(cam.far_clip))!r}"/>'
                f'<transform name="toWorld"><lookat origin="{v3(f32l(cam.origin))}" target="{v3(f32l(cam.target))}" '

@@ -98,6 +98,8 @@ class Scene:
         self._uv = []
         self.textures = []
         self.texture_bindings = []
+        # thin lens (pg_set_lens): (aperture radius, focus distance), or None: the pinhole of `camera`
+        self.lens = None
 
     # -- construction
     def add_material(self, m):
@@ -201,6 +203,15 @@ class Scene:
         c.fov_x_deg, c.near_clip, c.far_clip = fov_x, near, far
         c.width, c.height = width, height
         self.camera = c
+
+    def set_lens(self, aperture_radius, focus_distance=0.0):
+        """A thin lens in front of the camera (the reference's thinlens sensor): world-space aperture radius and the
+        distance of the focal plane along the viewing direction.  Radius 0 is the pinhole again.  The device wrapper
+        applies it after every upload (pg_set_lens)."""
+        r, f = float(aperture_radius), float(focus_distance)
+        if not (np.isfinite(r) and r >= 0 and np.isfinite(f)) or (r > 0 and not f > 0):
+            raise ValueError("set_lens: need a finite aperture radius >= 0 and, with a lens, a focus distance > 0")
+        self.lens = (r, f) if r > 0 else None
 
     def finalize(self):
         self.positions = np.ascontiguousarray(np.concatenate(self._pos), np.float32)

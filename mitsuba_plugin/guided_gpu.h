@@ -127,6 +127,8 @@ public:
         if (!m_flat.bindings.empty())
             check(pg_set_textures(m_ctx, m_flat.textures.data(), (uint32_t) m_flat.textures.size(), m_flat.bindings.data(),
                                   (uint32_t) m_flat.bindings.size(), m_flat.hasUV ? m_flat.uv.data() : NULL));
+        // the thinlens sensor's aperture and focal plane (flatten); the upload left the pinhole
+        if (m_flat.lensRadius > 0) check(pg_set_lens(m_ctx, m_flat.lensRadius, m_flat.focusDistance));
         // the film's reconstruction filter: any separable filter through its own discretised table
         // (rfilter.h:76-77); the box keeps the per-pixel film
         const ReconstructionFilter *rf = scene->getSensor()->getFilm()->getReconstructionFilter();
@@ -402,6 +404,7 @@ protected:
         std::vector<float> uv;
         bool hasUV = false;
         bool mirrorX = false, hasEnv = false;
+        float lensRadius = 0, focusDistance = 0;  // the thinlens sensor (pg_set_lens); radius 0: a pinhole
         void bind() {  // pg_upload_scene copies everything; the arrays live until then
             desc.num_vertices = (uint32_t) (pos.size() / 3);
             desc.num_triangles = (uint32_t) (idx.size() / 3);
@@ -788,6 +791,18 @@ inline GuidedGPUIntegrator::Flattened GuidedGPUIntegrator::flatten(const Scene *
     c.far_clip = (float) cam->getFarClip();
     c.width = (uint32_t) cam->getFilm()->getSize().x;
     c.height = (uint32_t) cam->getFilm()->getSize().y;
+    // ThinLens (thinlens.cpp:122) derives from PerspectiveCamera, so the cast above takes it: a sensor that asks for
+    // an aperture sample (sensor.h:303) must be that one, or it would be rendered as a pinhole without a word.  The
+    // class is private to its plugin: the radius comes from its properties (thinlens.cpp:132, a zero there became
+    // Epsilon, :134-137), the focus distance from ProjectiveCamera (sensor.h:455).
+    if (cam->needsApertureSample()) {
+        if (cam->getClass()->getName() != "ThinLens")
+            Log(EError, "guided_gpu: sensor %s needs an aperture sample and is not supported (perspective and thinlens "
+                "are)", cam->getClass()->getName().c_str());
+        const float radius = (float) cam->getProperties().getFloat("apertureRadius");
+        f.lensRadius = radius == 0 ? (float) Epsilon : radius;
+        f.focusDistance = (float) cam->getFocusDistance();
+    }
     f.desc.camera_medium = mediumOf(cam->getMedium());
     flattenEnvironment(scene, f);
     return f;  // the caller binds the descriptor's pointers (Flattened::bind) to its own copy
