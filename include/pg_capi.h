@@ -480,6 +480,47 @@ pg_status pg_get_lens(void *ctx, float *aperture_radius, float *focus_distance);
  * o_tmin: n x 4 floats (origin, tmin); d_tmax: n x 4 floats (direction, tmax). */
 pg_status pg_camera_rays(void *ctx, const uint32_t *pixels, const uint32_t *samples, uint32_t n, float *o_tmin,
                          float *d_tmax);
+/* ---- delta emitters: point, spot and directional lights in both integrators -----------------------------------------
+ * New entry points; pg_config, pg_stats, pg_scene_desc, pg_emitter and PG_ABI_VERSION are unchanged.  While none is
+ * set, no kernel compiled for them is launched by the path integrator and every result is bit for bit what it was.
+ *
+ * The emitters of a scene are picked uniformly (Scene::sampleEmitterDirect, scene.cpp:871-895):
+ *   ei = min((uint32_t)(sx * ne), ne - 1),  ne = area + delta + (envmap ? 1 : 0)
+ * area emitters first in their uploaded order, then the delta emitters in theirs, the environment emitter last.  The
+ * 1 / ne of the emitter-hit MIS weight counts all of them (Scene::pdfEmitterDirect).  A delta emitter's sample is in
+ * the discrete measure: its pdf is 1 / ne, its next-event contribution has MIS weight 1 (progressive_path.cpp:211,
+ * progressive_volpath.cpp:153,277) and at a guided vertex no D-tree pdf of its direction enters the weight.  It can
+ * never be hit.  With ref the shaded point (float32, no contraction):
+ *   point (point.cpp:131-147):  d = position - ref, dist = |d|, inv = 1 / dist, d *= inv;  value = intensity (inv inv)
+ *   spot (spot.cpp:105-125,184-200):  the point formula times the falloff of cosTheta = dot(-d, direction):
+ *          0 where cosTheta <= cos(cutoff_angle), 1 where cosTheta >= cos(beam_width), else
+ *          (cutoff_angle - acosf(cosTheta)) / (cutoff_angle - beam_width); the cosines and the reciprocal are computed
+ *          once by pg_set_delta_emitters.  No projection texture.
+ *   directional (directional.cpp:90-91,159-180):  with (centre, radius) the bounding sphere of the uploaded triangles'
+ *          box (its centre, 1.1 x its half diagonal) and diskCentre = centre - direction radius:
+ *          dist = dot(ref - diskCentre, direction), a failed sample where dist < 0;  d = -direction, value = intensity
+ * The shadow ray is the area emitters': origin ref, to dist (1 - ShadowEpsilon). */
+typedef enum { PG_EMITTER_POINT = 0, PG_EMITTER_SPOT = 1, PG_EMITTER_DIRECTIONAL = 2 } pg_delta_type;
+typedef struct pg_delta_emitter {
+    int32_t type;          /* pg_delta_type */
+    float position[3];     /* point, spot: toWorld * (0,0,0) */
+    float direction[3];    /* spot: the axis (toWorld * +z); directional: the direction the light travels; normalised
+                              on upload */
+    float intensity[3];    /* point, spot: W/sr (m_intensity); directional: irradiance on a surface normal to it
+                              (m_normalIrradiance) */
+    float cutoff_angle, beam_width;   /* spot, radians */
+} pg_delta_emitter;
+/* After pg_upload_scene and before the first render pass of that scene (PG_ERR_STATE otherwise); a later
+ * pg_upload_scene clears the delta emitters; n == 0 removes them, and the context is then bit for bit one on which
+ * the call was never made.  Both integrators.  The shadow-blocker list is emptied.  PG_ERR_INVALID, with the state
+ * left as it was: an unknown type, a non-finite field, a negative intensity, a zero direction of a spot or a
+ * directional light, a spot without 0 <= beam_width < cutoff_angle < pi, more than 65534 emitters in total. */
+pg_status pg_set_delta_emitters(void *ctx, const pg_delta_emitter *emitters, uint32_t n);
+/* Unit entry point (parity tests): the device function the shaders call for next-event estimation, over the scene's
+ * whole emitter set (area, delta, environment), at ref (n x 3) with a zero reference normal and samples (n x 2).
+ * out: n x 8 floats: d.xyz, dist, value / pdf (rgb, the emitter-pick probability included), measure (0 = the sample
+ * failed, 1 = solid angle, 2 = discrete). */
+pg_status pg_emitter_query(void *ctx, const float *ref, const float *samples, uint64_t n, float *out);
 pg_status pg_get_stats(void *ctx, pg_stats *stats);
 /* Path integrator: segments (counted in pg_stats.segments, not in escaped) whose hit was culled by the
  * closest-hit kernels since create: the ray's next vertex had already lost its Russian roulette, or was past the

@@ -76,6 +76,14 @@ class pg_texture_binding(C.Structure):
     _fields_ = [("material", C.c_uint32), ("texture", C.c_uint32)]
 
 
+PG_EMITTER_POINT, PG_EMITTER_SPOT, PG_EMITTER_DIRECTIONAL = 0, 1, 2
+
+
+class pg_delta_emitter(C.Structure):
+    _fields_ = [("type", C.c_int32), ("position", C.c_float * 3), ("direction", C.c_float * 3),
+                ("intensity", C.c_float * 3), ("cutoff_angle", C.c_float), ("beam_width", C.c_float)]
+
+
 class pg_camera(C.Structure):
     _fields_ = [("origin", C.c_float * 3), ("target", C.c_float * 3), ("up", C.c_float * 3),
                 ("fov_x_deg", C.c_float), ("near_clip", C.c_float), ("far_clip", C.c_float),
@@ -196,6 +204,8 @@ SIGNATURES = [
     ("pg_set_lens", C.c_int32, [VP, C.c_float, C.c_float]),
     ("pg_get_lens", C.c_int32, [VP, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     ("pg_camera_rays", C.c_int32, [VP, VP, VP, C.c_uint32, VP, VP]),
+    ("pg_set_delta_emitters", C.c_int32, [VP, C.POINTER(pg_delta_emitter), C.c_uint32]),
+    ("pg_emitter_query", C.c_int32, [VP, VP, VP, C.c_uint64, VP]),
     ("pg_get_stats", C.c_int32, [VP, C.POINTER(pg_stats)]),
     ("pg_get_culled", C.c_int32, [VP, C.POINTER(C.c_uint64)]),
     ("pg_get_probes", C.c_int32, [VP, C.POINTER(C.c_uint64)]),

@@ -97,13 +97,7 @@ bool buildEnvTables(const pg_envmap &e, const float lo[3], const float hi[3], En
     out.pixel_size[0] = (float)(2 * M_PI / W);
     out.pixel_size[1] = (float)(M_PI / H);
     // createShape (envmap.cpp:331-356): the scene AABB's bounding sphere, radius x 1.5
-    float r2 = 0;
-    for (int a = 0; a < 3; ++a) {
-        out.center[a] = (lo[a] + hi[a]) * 0.5f;
-        const float d = hi[a] - out.center[a];
-        r2 += d * d;
-    }
-    out.radius = std::max(1e-4f, std::sqrt(r2) * 1.5f);
+    out.radius = std::max(1e-4f, boxSphere(lo, hi, out.center) * 1.5f);
     return true;
 }
 

@@ -3,6 +3,7 @@
 #pragma once
 #include <stdint.h>
 
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -24,6 +25,18 @@ struct EnvTables {
 
 // IEEE binary16 round-to-nearest-even of a float, returned as float (the MIP map's SpectrumHalf storage)
 float roundToHalf(float f);
+
+// AABB::getBSphere (aabb.h): the centre of the box (lo, hi) and its half diagonal, in float32.  The environment
+// emitter's sphere is 1.5 x that radius (envmap.cpp:331-356), a directional emitter's 1.1 x (directional.cpp:90-91).
+inline float boxSphere(const float lo[3], const float hi[3], float center[3]) {
+    float r2 = 0;
+    for (int a = 0; a < 3; ++a) {
+        center[a] = (lo[a] + hi[a]) * 0.5f;
+        const float d = hi[a] - center[a];
+        r2 += d * d;
+    }
+    return std::sqrt(r2);
+}
 
 // Validates `e` and fills `out`; lo/hi = the scene AABB (the bounding sphere's box).  false + err on
 // bad input (empty, non-finite, all black: envmap.cpp:312-316 rejects the last two as well).

@@ -240,6 +240,11 @@ struct Ctx {
     std::vector<uint32_t> host_indices;  // the uploaded scene's triangles (their vertices' texcoords)
     uint32_t num_vertices = 0;
     float scene_lo[3] = {0, 0, 0}, scene_hi[3] = {0, 0, 0};
+    // delta emitters (pg_set_delta_emitters): nothing is allocated while num_delta is 0.  tri_lo / tri_hi: the
+    // uploaded triangles' box, whose bounding sphere a directional emitter's disk lies on
+    DevBuf delta;
+    uint32_t num_delta = 0, num_area = 0;
+    float tri_lo[3] = {0, 0, 0}, tri_hi[3] = {0, 0, 0};
     // shard
     std::vector<uint32_t> local_pixels;
     DevBuf d_local_pixels;
@@ -449,6 +454,7 @@ SceneDev sceneView(const Ctx *c) {
         sc.tex = c->tex.as<GTex>();
         sc.mtex = c->mtex.as<uint32_t>();
     }
+    if (c->num_delta) sc.delta = c->delta.as<GDelta>();
     return sc;
 }
 
@@ -1311,6 +1317,91 @@ pg_status pg_hit_uvs(void *ctx, const float *rays, uint64_t n, float *out) {
     return PG_OK;
 }
 
+// ---- delta emitters (pg_capi.h pg_set_delta_emitters) ----------------------------------------------------------------
+pg_status pg_set_delta_emitters(void *ctx, const pg_delta_emitter *emitters, uint32_t n) {
+    Ctx *c = (Ctx *)ctx;
+    if (!c) return fail(nullptr, PG_ERR_INVALID, "pg_set_delta_emitters: null context");
+    if (!c->has_scene) return fail(c, PG_ERR_STATE, "pg_set_delta_emitters: no scene uploaded");
+    if (c->scene_rendered)
+        return fail(c, PG_ERR_STATE, "pg_set_delta_emitters: a render pass has already run on this scene");
+    if (n && !emitters) return fail(c, PG_ERR_INVALID, "pg_set_delta_emitters: null argument");
+    if ((uint64_t)c->num_area + n + (c->has_env ? 1u : 0u) > 65534)
+        return fail(c, PG_ERR_INVALID, "pg_set_delta_emitters: more than 65534 emitters");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    // validate everything before anything changes
+    float center[3];
+    const float radius = pgh::boxSphere(c->tri_lo, c->tri_hi, center) * 1.1f;
+    std::vector<GDelta> recs(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        const pg_delta_emitter &e = emitters[i];
+        const std::string id = "pg_set_delta_emitters: emitter " + std::to_string(i) + ": ";
+        if (e.type != PG_EMITTER_POINT && e.type != PG_EMITTER_SPOT && e.type != PG_EMITTER_DIRECTIONAL)
+            return fail(c, PG_ERR_INVALID, id + "unknown type");
+        for (int k = 0; k < 3; ++k) {
+            if (!std::isfinite(e.position[k]) || !std::isfinite(e.direction[k]) || !std::isfinite(e.intensity[k]))
+                return fail(c, PG_ERR_INVALID, id + "non-finite field");
+            if (e.intensity[k] < 0) return fail(c, PG_ERR_INVALID, id + "negative intensity");
+        }
+        if (!std::isfinite(e.cutoff_angle) || !std::isfinite(e.beam_width))
+            return fail(c, PG_ERR_INVALID, id + "non-finite field");
+        GDelta &g = recs[i];
+        g = GDelta{};
+        g.type = (uint32_t)e.type;
+        for (int k = 0; k < 3; ++k) g.intensity[k] = e.intensity[k];
+        if (e.type != PG_EMITTER_POINT) {
+            const float l = std::sqrt(e.direction[0] * e.direction[0] + e.direction[1] * e.direction[1] +
+                                      e.direction[2] * e.direction[2]);
+            if (!(l > 0) || !std::isfinite(l)) return fail(c, PG_ERR_INVALID, id + "zero direction");
+            for (int k = 0; k < 3; ++k) g.dir[k] = e.direction[k] / l;
+        }
+        if (e.type == PG_EMITTER_DIRECTIONAL) {  // the disk's centre (directional.cpp:159-180)
+            for (int k = 0; k < 3; ++k) g.pos[k] = center[k] - g.dir[k] * radius;
+        } else {
+            for (int k = 0; k < 3; ++k) g.pos[k] = e.position[k];
+        }
+        if (e.type == PG_EMITTER_SPOT) {  // SpotEmitter::configure (spot.cpp:105-112)
+            if (!(e.beam_width >= 0 && e.beam_width < e.cutoff_angle && e.cutoff_angle < 3.14159265358979323846f))
+                return fail(c, PG_ERR_INVALID, id + "a spot needs 0 <= beam_width < cutoff_angle < pi");
+            g.cutoff = e.cutoff_angle;
+            g.cos_cutoff = std::cos(e.cutoff_angle);
+            g.cos_beam = std::cos(e.beam_width);
+            g.inv_transition = 1.0f / (e.cutoff_angle - e.beam_width);
+        }
+    }
+    if (n) {
+        DevBuf nb;
+        HIPC(c, nb.alloc((size_t)n * sizeof(GDelta)));
+        HIPC(c, hipMemcpy(nb.p, recs.data(), (size_t)n * sizeof(GDelta), hipMemcpyHostToDevice));
+        std::swap(c->delta.p, nb.p);
+        std::swap(c->delta.bytes, nb.bytes);
+    } else {
+        c->delta.release();
+    }
+    c->num_delta = n;
+    c->g.num_emitters = c->num_area + n + (c->has_env ? 1u : 0u);
+    return resetBlockers(c);
+}
+
+pg_status pg_emitter_query(void *ctx, const float *ref, const float *samples, uint64_t n, float *out) {
+    Ctx *c = (Ctx *)ctx;
+    if (!c || (n && (!ref || !samples || !out))) return fail(c, PG_ERR_INVALID, "pg_emitter_query: null argument");
+    if (!c->has_scene) return fail(c, PG_ERR_STATE, "pg_emitter_query: no scene");
+    if (n > 0xFFFFFFFFull / 8) return fail(c, PG_ERR_INVALID, "pg_emitter_query: too many points");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    if (!n) return PG_OK;
+    DevBuf r, s, o;
+    HIPC(c, r.alloc(n * 12));
+    HIPC(c, s.alloc(n * 8));
+    HIPC(c, o.alloc(n * 32));
+    HIPC(c, hipMemcpyAsync(r.p, ref, n * 12, hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipMemcpyAsync(s.p, samples, n * 8, hipMemcpyHostToDevice, c->stream));
+    pg_launch_emitter_query(c->stream, c->g, sceneView(c), r.as<float>(), s.as<float>(), (uint32_t)n, o.as<float>());
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipMemcpyAsync(out, o.p, n * 32, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    return PG_OK;
+}
+
 pg_status pg_read_film_filtered(void *ctx, float *rgbw, int64_t *raw) {
     Ctx *c = (Ctx *)ctx;
     if (!c) return fail(nullptr, PG_ERR_INVALID, "pg_read_film_filtered: null context");
@@ -1604,7 +1695,16 @@ pg_status pg_upload_scene(void *ctx, const pg_scene_desc *d) {
     g.width = cam.width;
     g.height = cam.height;
     g.num_emitters = d->num_emitters + (d->envmap ? 1u : 0u);
+    g.num_area = d->num_emitters;
     g.num_materials = d->num_materials;
+    // a new scene has no delta emitters (pg_set_delta_emitters)
+    c->num_area = d->num_emitters;
+    c->num_delta = 0;
+    c->delta.release();
+    for (int a = 0; a < 3; ++a) {
+        c->tri_lo[a] = bvh.lo[a];
+        c->tri_hi[a] = bvh.hi[a];
+    }
 
     // tile shard of this rank: 32x32 tiles dealt round-robin
     const uint32_t T = c->cfg.tile_size, tx = (cam.width + T - 1) / T, ty = (cam.height + T - 1) / T;

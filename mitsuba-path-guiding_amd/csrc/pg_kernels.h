@@ -33,6 +33,8 @@ struct SceneDev {
     const float4 *tuv;      // PG_TRI_UV_F4 float4 per BVH-order triangle: the vertices' texcoords
     const GTex *tex;
     const uint32_t *mtex;   // per material: the texture bound to its diffuse reflectance, ~0 = none
+    // delta emitters (pg_set_delta_emitters): emitters [g.num_area, g.num_area + their count); nullptr while none is set
+    const GDelta *delta;
 };
 
 // float4 per training vertex: (x, woPdf), (T after the vertex, packed canonical wo), (L snapshot, -),
@@ -236,6 +238,10 @@ void pg_launch_film_filtered(hipStream_t s, const GParams &g, const SceneDev &sc
                              uint32_t sample_base, uint32_t tile0, uint32_t ntiles);
 // unit-level environment-emitter queries (pg_envmap_query)
 void pg_launch_envmap_query(hipStream_t s, const SceneDev &sc, int op, const float *in, uint32_t n, float *out);
+// unit-level emitter sampling (pg_emitter_query): sampleEmitter over area, delta and environment emitters at ref
+// (n x 3) with refN = 0 and samples smp (n x 2); out n x 8
+void pg_launch_emitter_query(hipStream_t s, const GParams &g, const SceneDev &sc, const float *ref, const float *smp,
+                             uint32_t n, float *out);
 // p.pinfo == nullptr: the vertex count of slot i is bits(p.rad[i].w) (volpath items)
 // env_hits: surface path with an environment emitter (escape radiance in the hit record)
 void pg_launch_commit(hipStream_t s, const PathDev &p, uint32_t nslots, int max_vertices, pg_record *records,

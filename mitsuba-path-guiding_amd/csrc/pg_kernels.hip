@@ -610,7 +610,9 @@ extern "C" int pg_debug_watch_read(float *out, uint32_t max, uint32_t *n) {
 // TEX (the textured class, pg_layout.h PG_CLASS_TEXTURED): the vertex's material has a texture as its diffuse
 // reflectance.  The lookup replaces the register copy of GMat::diff and the albedo bound, and the BSDF code runs on
 // that copy unchanged; with TEX = false none of it is compiled.
-template <int MODEL, bool CAN_GUIDE, bool ENV, bool TEX = false>
+// DELTA: delta emitters are set (pg_set_delta_emitters): sampleEmitter's point / spot / directional branches and the
+// discrete-measure rule of the NEE below; with DELTA = false none of it is compiled.
+template <int MODEL, bool CAN_GUIDE, bool ENV, bool TEX = false, bool DELTA = false>
 __device__ __forceinline__ void shadeOne(const GParams &g, const SceneDev &sc, const SDDev &sd, const PathDev &p,
                                          uint32_t slot, const GMat *mats, bool wantKey, bool &alive, bool &shadow,
                                          bool &probe, uint32_t &rkey, uint32_t &blocked) {
@@ -784,7 +786,8 @@ __device__ __forceinline__ void shadeOne(const GParams &g, const SceneDev &sc, c
             float s0, s1;
             rng2(key, sample, dimOf(depth, SLOT_NEE), s0, s1);
             float emPdf;
-            f3 value = sampleEmitter<ENV>(g, sc, h.p, refN, s0, s1, neeD, neeDist, emPdf);
+            bool discrete = false;  // a delta emitter's sample: MIS weight 1, no D-tree pdf of its direction
+            f3 value = sampleEmitter<ENV, DELTA>(g, sc, h.p, refN, s0, s1, neeD, neeDist, emPdf, nullptr, &discrete);
             if (!isZero(value)) {
                 f3 woL = h.sh.toLocal(neeD);
                 f3 bsdfVal = bsdfEval<MODEL>(M, h.wi, woL);
@@ -802,7 +805,8 @@ __device__ __forceinline__ void shadeOne(const GParams &g, const SceneDev &sc, c
                                                        shadowTmin(f4(h.p, 0.0f)), neeDist * (1 - kShadowEpsilon));
                         shadow = blocked == 0;
                     }
-                    if (guide) neePending = shadow;  // a resolved ray's contribution is never used
+                    if (DELTA && discrete) neeC = neeV;
+                    else if (guide) neePending = shadow;  // a resolved ray's contribution is never used
                     else neeC = neeV * miWeight(emPdf, neeBp);
                 }
             }
@@ -945,7 +949,7 @@ __device__ __forceinline__ void shadeOne(const GParams &g, const SceneDev &sc, c
 #endif
 }
 
-template <int MODEL, bool CAN_GUIDE, bool ENV, bool TEX = false>
+template <int MODEL, bool CAN_GUIDE, bool ENV, bool TEX = false, bool DELTA = false>
 __device__ __forceinline__ void shadeBlock(const GParams &g, const SceneDev &sc, const SDDev &sd, const PathDev &p,
                                            const Queue &in, const Queue &out, const Queue &shq, const Queue &pq,
                                            uint32_t bid) {
@@ -970,7 +974,7 @@ __device__ __forceinline__ void shadeBlock(const GParams &g, const SceneDev &sc,
         __syncthreads();
     }
     if (i < n)
-        shadeOne<MODEL, CAN_GUIDE, ENV, TEX>(g, sc, sd, p, slot, ldsMats ? reinterpret_cast<const GMat *>(smat) : sc.mats,
+        shadeOne<MODEL, CAN_GUIDE, ENV, TEX, DELTA>(g, sc, sd, p, slot, ldsMats ? reinterpret_cast<const GMat *>(smat) : sc.mats,
                                         out.keys != nullptr, alive, shadow, probe, rkey, blocked);
     if (out.keys)
         waveAppendKey(alive, slot, (uint16_t)rkey, out.items + (size_t)s * out.stride, out.keys + (size_t)s * out.stride,
@@ -995,10 +999,10 @@ __device__ __forceinline__ void shadeBlock(const GParams &g, const SceneDev &sc,
     }
 }
 
-template <int MODEL, bool CAN_GUIDE, bool ENV, bool TEX = false>
+template <int MODEL, bool CAN_GUIDE, bool ENV, bool TEX = false, bool DELTA = false>
 __global__ __launch_bounds__(SHADE_BLOCK) void k_shade(GParams g, SceneDev sc, SDDev sd, PathDev p, Queue in,
                                                        Queue out, Queue shq, Queue pq) {
-    shadeBlock<MODEL, CAN_GUIDE, ENV, TEX>(g, sc, sd, p, in, out, shq, pq, blockIdx.x);
+    shadeBlock<MODEL, CAN_GUIDE, ENV, TEX, DELTA>(g, sc, sd, p, in, out, shq, pq, blockIdx.x);
 }
 
 // every material class of a bounce in one launch (no environment emitter): blocks
@@ -1012,19 +1016,20 @@ struct ShadeRanges {
 #endif
 // TEX: the scene has textures bound (pg_set_textures): the instantiation with the textured class' body.  Scenes
 // without textures launch k_shade_all<false>, which holds the six bodies it always did and nothing else.
-template <bool TEX>
+// DELTA: delta emitters are set (pg_set_delta_emitters): every body with the delta NEE compiled in.
+template <bool TEX, bool DELTA = false>
 __global__ __launch_bounds__(SHADE_BLOCK) __attribute__((amdgpu_waves_per_eu(PG_SHADE_WAVES))) void k_shade_all(
     GParams g, SceneDev sc, SDDev sd, PathDev p, ClassQueues in, Queue out, Queue shq, Queue pq, ShadeRanges r) {
     static_assert(PG_NUM_CLASSES == 7, "class ranges");
     const uint32_t b = blockIdx.x;
-    if (b < r.end[0]) shadeBlock<PG_BSDF_DIFFUSE, true, false>(g, sc, sd, p, in.q[0], out, shq, pq, b);
-    else if (b < r.end[1]) shadeBlock<PG_BSDF_ROUGHCONDUCTOR, true, false>(g, sc, sd, p, in.q[1], out, shq, pq, b - r.end[0]);
-    else if (b < r.end[2]) shadeBlock<PG_BSDF_ROUGHDIELECTRIC, true, false>(g, sc, sd, p, in.q[2], out, shq, pq, b - r.end[1]);
-    else if (b < r.end[3]) shadeBlock<PG_BSDF_PLASTIC, false, false>(g, sc, sd, p, in.q[3], out, shq, pq, b - r.end[2]);
-    else if (b < r.end[4]) shadeBlock<PG_BSDF_ROUGHPLASTIC, true, false>(g, sc, sd, p, in.q[4], out, shq, pq, b - r.end[3]);
-    else if (!TEX || b < r.end[5]) shadeBlock<-1, false, false>(g, sc, sd, p, in.q[5], out, shq, pq, b - r.end[4]);
+    if (b < r.end[0]) shadeBlock<PG_BSDF_DIFFUSE, true, false, false, DELTA>(g, sc, sd, p, in.q[0], out, shq, pq, b);
+    else if (b < r.end[1]) shadeBlock<PG_BSDF_ROUGHCONDUCTOR, true, false, false, DELTA>(g, sc, sd, p, in.q[1], out, shq, pq, b - r.end[0]);
+    else if (b < r.end[2]) shadeBlock<PG_BSDF_ROUGHDIELECTRIC, true, false, false, DELTA>(g, sc, sd, p, in.q[2], out, shq, pq, b - r.end[1]);
+    else if (b < r.end[3]) shadeBlock<PG_BSDF_PLASTIC, false, false, false, DELTA>(g, sc, sd, p, in.q[3], out, shq, pq, b - r.end[2]);
+    else if (b < r.end[4]) shadeBlock<PG_BSDF_ROUGHPLASTIC, true, false, false, DELTA>(g, sc, sd, p, in.q[4], out, shq, pq, b - r.end[3]);
+    else if (!TEX || b < r.end[5]) shadeBlock<-1, false, false, false, DELTA>(g, sc, sd, p, in.q[5], out, shq, pq, b - r.end[4]);
     else if constexpr (TEX)
-        shadeBlock<PG_MODELS_DIFFUSE_SLOT, true, false, true>(g, sc, sd, p, in.q[6], out, shq, pq, b - r.end[5]);
+        shadeBlock<PG_MODELS_DIFFUSE_SLOT, true, false, true, DELTA>(g, sc, sd, p, in.q[6], out, shq, pq, b - r.end[5]);
 }
 
 // ---- counting sort of a queue's shards by ray order key (PG_RAY_SORT): the next closest-hit launch
@@ -1113,7 +1118,7 @@ __global__ __launch_bounds__(256) void k_rsort_scatter(Queue q, uint32_t *hist, 
 // the bounce-by-bounce loop.  Input: the queue of the bounce just traced (hits already in p.hit).
 // stats: [0] traced segments, [1] escaped segments, [2] shadow rays, [3] culled hits, [4] probed segments (u64,
 // device atomics; a probe is also a segment and either a culled hit or an escape).
-template <bool ENV, bool TEX>
+template <bool ENV, bool TEX, bool DELTA>
 __device__ __forceinline__ void tailShade(const GParams &g, const SceneDev &sc, const SDDev &sd, const PathDev &p,
                                           uint32_t slot, uint32_t tri, bool &alive, bool &shadow, bool &probe,
                                           uint32_t &blocked) {
@@ -1121,23 +1126,23 @@ __device__ __forceinline__ void tailShade(const GParams &g, const SceneDev &sc, 
     // the textured class: only scenes with textures bound have such triangles, and they run k_tail<.., TEX = true>
     if constexpr (TEX) {
         if ((sc.tclass[tri] & PG_TCLASS_MASK) == PG_CLASS_TEXTURED) {
-            shadeOne<PG_MODELS_DIFFUSE_SLOT, true, ENV, true>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, probe, rk, blocked);
+            shadeOne<PG_MODELS_DIFFUSE_SLOT, true, ENV, true, DELTA>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, probe, rk, blocked);
             return;
         }
     }
     switch (sc.tclass[tri] & PG_TCLASS_MASK) {
-        case PG_CLASS_DIFFUSE: shadeOne<PG_BSDF_DIFFUSE, true, ENV>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, probe, rk, blocked); break;
+        case PG_CLASS_DIFFUSE: shadeOne<PG_BSDF_DIFFUSE, true, ENV, false, DELTA>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, probe, rk, blocked); break;
         case PG_CLASS_ROUGHCONDUCTOR:
-            shadeOne<PG_BSDF_ROUGHCONDUCTOR, true, ENV>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, probe, rk, blocked);
+            shadeOne<PG_BSDF_ROUGHCONDUCTOR, true, ENV, false, DELTA>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, probe, rk, blocked);
             break;
         case PG_CLASS_ROUGHDIELECTRIC:
-            shadeOne<PG_BSDF_ROUGHDIELECTRIC, true, ENV>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, probe, rk, blocked);
+            shadeOne<PG_BSDF_ROUGHDIELECTRIC, true, ENV, false, DELTA>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, probe, rk, blocked);
             break;
-        case PG_CLASS_PLASTIC: shadeOne<PG_BSDF_PLASTIC, false, ENV>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, probe, rk, blocked); break;
+        case PG_CLASS_PLASTIC: shadeOne<PG_BSDF_PLASTIC, false, ENV, false, DELTA>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, probe, rk, blocked); break;
         case PG_CLASS_ROUGHPLASTIC:
-            shadeOne<PG_BSDF_ROUGHPLASTIC, true, ENV>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, probe, rk, blocked);
+            shadeOne<PG_BSDF_ROUGHPLASTIC, true, ENV, false, DELTA>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, probe, rk, blocked);
             break;
-        default: shadeOne<-1, false, ENV>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, probe, rk, blocked);
+        default: shadeOne<-1, false, ENV, false, DELTA>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, probe, rk, blocked);
     }
 }
 #ifndef PG_TAIL_WAVES
@@ -1146,7 +1151,7 @@ __device__ __forceinline__ void tailShade(const GParams &g, const SceneDev &sc, 
 // COUNT: the recording passes' instantiation (shadowRows).  On the sampled rows, one plain add per occluded ray to its
 // triangle's counter and one per shadow ray, occluded or not, to the single total: the one-address pattern that is too
 // slow for the bounce launches' rows, affordable here because the tail holds few paths
-template <bool ENV, bool COUNT = false, bool TEX = false>
+template <bool ENV, bool COUNT = false, bool TEX = false, bool DELTA = false>
 __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PG_TAIL_WAVES > 0 ? PG_TAIL_WAVES : 1))) void k_tail(GParams g, SceneDev sc, SDDev sd, PathDev p, Queue q,
                                                       unsigned long long *stats) {
     __shared__ uint32_t stack[2 * WIDE_LDS_STACK * TRACE_BLOCK];  // >= LDS_STACK words per thread
@@ -1162,7 +1167,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PG_
         while (tri != 0xFFFFFFFFu) {
             bool alive = false, shadow = false, probe = false;
             uint32_t blocked = 0;
-            tailShade<ENV, TEX>(g, sc, sd, p, slot, tri, alive, shadow, probe, blocked);
+            tailShade<ENV, TEX, DELTA>(g, sc, sd, p, slot, tri, alive, shadow, probe, blocked);
             if (!ENV && blocked) {  // a shadow ray the blocker list resolved: counted, not traced
                 ++shadows;
                 ++drops;
@@ -1860,39 +1865,43 @@ void pg_launch_trace(hipStream_t s, const GParams &g, const SceneDev &sc, const 
         else hipLaunchKernelGGL((k_trace<false, false>), grid, dim3(TRACE_BLOCK), 0, s, g, sc, p, q, cq, first);
     }
 }
-template <bool ENV>
+template <bool ENV, bool DELTA>
 static void launchShade(hipStream_t s, int cls, dim3 grid, const GParams &g, const SceneDev &sc, const SDDev &sd,
                         const PathDev &p, Queue in, Queue out, Queue shq, Queue pq) {
     const dim3 block(SHADE_BLOCK);
     switch (cls) {
         case PG_CLASS_DIFFUSE:
-            hipLaunchKernelGGL((k_shade<PG_BSDF_DIFFUSE, true, ENV>), grid, block, 0, s, g, sc, sd, p, in, out, shq, pq);
+            hipLaunchKernelGGL((k_shade<PG_BSDF_DIFFUSE, true, ENV, false, DELTA>), grid, block, 0, s, g, sc, sd, p, in, out, shq, pq);
             break;
         case PG_CLASS_ROUGHCONDUCTOR:
-            hipLaunchKernelGGL((k_shade<PG_BSDF_ROUGHCONDUCTOR, true, ENV>), grid, block, 0, s, g, sc, sd, p, in, out, shq, pq);
+            hipLaunchKernelGGL((k_shade<PG_BSDF_ROUGHCONDUCTOR, true, ENV, false, DELTA>), grid, block, 0, s, g, sc, sd, p, in, out, shq, pq);
             break;
         case PG_CLASS_ROUGHDIELECTRIC:
-            hipLaunchKernelGGL((k_shade<PG_BSDF_ROUGHDIELECTRIC, true, ENV>), grid, block, 0, s, g, sc, sd, p, in, out, shq, pq);
+            hipLaunchKernelGGL((k_shade<PG_BSDF_ROUGHDIELECTRIC, true, ENV, false, DELTA>), grid, block, 0, s, g, sc, sd, p, in, out, shq, pq);
             break;
         case PG_CLASS_PLASTIC:
-            hipLaunchKernelGGL((k_shade<PG_BSDF_PLASTIC, false, ENV>), grid, block, 0, s, g, sc, sd, p, in, out, shq, pq);
+            hipLaunchKernelGGL((k_shade<PG_BSDF_PLASTIC, false, ENV, false, DELTA>), grid, block, 0, s, g, sc, sd, p, in, out, shq, pq);
             break;
         case PG_CLASS_ROUGHPLASTIC:
-            hipLaunchKernelGGL((k_shade<PG_BSDF_ROUGHPLASTIC, true, ENV>), grid, block, 0, s, g, sc, sd, p, in, out, shq, pq);
+            hipLaunchKernelGGL((k_shade<PG_BSDF_ROUGHPLASTIC, true, ENV, false, DELTA>), grid, block, 0, s, g, sc, sd, p, in, out, shq, pq);
             break;
         case PG_CLASS_TEXTURED:  // a textured diffuse reflectance (diffuse, plastic, roughplastic at run time)
-            hipLaunchKernelGGL((k_shade<PG_MODELS_DIFFUSE_SLOT, true, ENV, true>), grid, block, 0, s, g, sc, sd, p, in, out, shq, pq);
+            hipLaunchKernelGGL((k_shade<PG_MODELS_DIFFUSE_SLOT, true, ENV, true, DELTA>), grid, block, 0, s, g, sc, sd, p, in, out, shq, pq);
             break;
         default:  // delta lobes: conductor, dielectric (runtime switch, never guided)
-            hipLaunchKernelGGL((k_shade<-1, false, ENV>), grid, block, 0, s, g, sc, sd, p, in, out, shq, pq);
+            hipLaunchKernelGGL((k_shade<-1, false, ENV, false, DELTA>), grid, block, 0, s, g, sc, sd, p, in, out, shq, pq);
     }
 }
 void pg_launch_shade_class(hipStream_t s, int cls, const GParams &g, const SceneDev &sc, const SDDev &sd,
                            const PathDev &p, Queue in, uint32_t max_shard, Queue out, Queue shq, Queue pq) {
     if (!max_shard) return;
     const dim3 grid = shardGrid(max_shard, SHADE_BLOCK, 0xFFFFFFFFu);
-    if (sc.env) launchShade<true>(s, cls, grid, g, sc, sd, p, in, out, shq, pq);
-    else launchShade<false>(s, cls, grid, g, sc, sd, p, in, out, shq, pq);
+    // sc.delta: delta emitters are set (pg_set_delta_emitters); scenes without them launch the kernels they always did
+    if (sc.delta) {
+        if (sc.env) launchShade<true, true>(s, cls, grid, g, sc, sd, p, in, out, shq, pq);
+        else launchShade<false, true>(s, cls, grid, g, sc, sd, p, in, out, shq, pq);
+    } else if (sc.env) launchShade<true, false>(s, cls, grid, g, sc, sd, p, in, out, shq, pq);
+    else launchShade<false, false>(s, cls, grid, g, sc, sd, p, in, out, shq, pq);
 }
 void pg_launch_shade_all(hipStream_t s, const GParams &g, const SceneDev &sc, const SDDev &sd, const PathDev &p,
                          const Queue *class_queues, const uint32_t *max_shard, Queue out, Queue shq, Queue pq) {
@@ -1906,7 +1915,10 @@ void pg_launch_shade_all(hipStream_t s, const GParams &g, const SceneDev &sc, co
     }
     for (int c = PG_NUM_CLASSES; c < PG_CLASS_ROWS; ++c) cq.q[c] = class_queues[c];
     if (!total) return;
-    if (sc.mtex) hipLaunchKernelGGL(k_shade_all<true>, dim3(total), dim3(SHADE_BLOCK), 0, s, g, sc, sd, p, cq, out, shq, pq, r);
+    if (sc.delta) {
+        if (sc.mtex) hipLaunchKernelGGL((k_shade_all<true, true>), dim3(total), dim3(SHADE_BLOCK), 0, s, g, sc, sd, p, cq, out, shq, pq, r);
+        else hipLaunchKernelGGL((k_shade_all<false, true>), dim3(total), dim3(SHADE_BLOCK), 0, s, g, sc, sd, p, cq, out, shq, pq, r);
+    } else if (sc.mtex) hipLaunchKernelGGL(k_shade_all<true>, dim3(total), dim3(SHADE_BLOCK), 0, s, g, sc, sd, p, cq, out, shq, pq, r);
     else hipLaunchKernelGGL(k_shade_all<false>, dim3(total), dim3(SHADE_BLOCK), 0, s, g, sc, sd, p, cq, out, shq, pq, r);
 }
 // the recording passes count shadow blockers (sc.blk_counts is set only for them, never with an environment emitter)
@@ -1953,6 +1965,17 @@ void pg_launch_tail(hipStream_t s, const GParams &g, const SceneDev &sc, const S
     // at most TRACE_MAX_BLOCKS blocks (a grid-stride loop over each shard): the traversal stacks' overflow
     // ring (threadStack / threadWideStack, stride gridDim.x * TRACE_BLOCK) holds that many threads
     const dim3 grid = shardGrid(max_shard, TRACE_BLOCK, TRACE_MAX_BLOCKS / PG_QSHARDS);
+    if (sc.delta) {  // delta emitters set: the instantiations with their NEE compiled in
+        const bool count = blockersCounted(g, sc);
+        if (sc.mtex) {
+            if (sc.env) hipLaunchKernelGGL((k_tail<true, false, true, true>), grid, dim3(TRACE_BLOCK), 0, s, g, sc, sd, p, q, stats);
+            else if (count) hipLaunchKernelGGL((k_tail<false, true, true, true>), grid, dim3(TRACE_BLOCK), 0, s, g, sc, sd, p, q, stats);
+            else hipLaunchKernelGGL((k_tail<false, false, true, true>), grid, dim3(TRACE_BLOCK), 0, s, g, sc, sd, p, q, stats);
+        } else if (sc.env) hipLaunchKernelGGL((k_tail<true, false, false, true>), grid, dim3(TRACE_BLOCK), 0, s, g, sc, sd, p, q, stats);
+        else if (count) hipLaunchKernelGGL((k_tail<false, true, false, true>), grid, dim3(TRACE_BLOCK), 0, s, g, sc, sd, p, q, stats);
+        else hipLaunchKernelGGL((k_tail<false, false, false, true>), grid, dim3(TRACE_BLOCK), 0, s, g, sc, sd, p, q, stats);
+        return;
+    }
     if (sc.mtex) {  // textures bound: the instantiations with the textured class' body
         if (sc.env) hipLaunchKernelGGL((k_tail<true, false, true>), grid, dim3(TRACE_BLOCK), 0, s, g, sc, sd, p, q, stats);
         else if (blockersCounted(g, sc)) hipLaunchKernelGGL((k_tail<false, true, true>), grid, dim3(TRACE_BLOCK), 0, s, g, sc, sd, p, q, stats);
@@ -2032,6 +2055,35 @@ __global__ __launch_bounds__(256) void k_envmap_query(SceneDev sc, int op, const
 void pg_launch_envmap_query(hipStream_t s, const SceneDev &sc, int op, const float *in, uint32_t n, float *out) {
     if (!n) return;
     hipLaunchKernelGGL(k_envmap_query, dim3(blocks(n, 256)), dim3(256), 0, s, sc, op, in, n, out);
+}
+// unit-level emitter sampling (pg_emitter_query): the shaders' sampleEmitter over the scene's whole emitter set at
+// ref[i] with refN = 0; out n x 8: d, dist, value / pdf, measure (0 failed, 1 solid angle, 2 discrete)
+template <bool ENV>
+__global__ __launch_bounds__(256) void k_emitter_query(GParams g, SceneDev sc, const float *ref, const float *smp, uint32_t n,
+                                                       float *out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    f3 d = mk1(0.f);
+    float dist = 0, pdf;
+    bool discrete = false;
+    const f3 v = sampleEmitter<ENV, true>(g, sc, mk(ref[3 * (size_t)i], ref[3 * (size_t)i + 1], ref[3 * (size_t)i + 2]), mk1(0.f),
+                                          smp[2 * (size_t)i], smp[2 * (size_t)i + 1], d, dist, pdf, nullptr, &discrete);
+    const bool ok = pdf != 0 && !isZero(v);
+    float *o = out + 8 * (size_t)i;
+    o[0] = ok ? d.x : 0.0f;
+    o[1] = ok ? d.y : 0.0f;
+    o[2] = ok ? d.z : 0.0f;
+    o[3] = ok ? dist : 0.0f;
+    o[4] = ok ? v.x : 0.0f;
+    o[5] = ok ? v.y : 0.0f;
+    o[6] = ok ? v.z : 0.0f;
+    o[7] = !ok ? 0.0f : discrete ? 2.0f : 1.0f;
+}
+void pg_launch_emitter_query(hipStream_t s, const GParams &g, const SceneDev &sc, const float *ref, const float *smp,
+                             uint32_t n, float *out) {
+    if (!n) return;
+    if (sc.env) hipLaunchKernelGGL(k_emitter_query<true>, dim3(blocks(n, 256)), dim3(256), 0, s, g, sc, ref, smp, n, out);
+    else hipLaunchKernelGGL(k_emitter_query<false>, dim3(blocks(n, 256)), dim3(256), 0, s, g, sc, ref, smp, n, out);
 }
 void pg_launch_commit(hipStream_t s, const PathDev &p, uint32_t nslots, int max_vertices, pg_record *records,
                       unsigned long long *rec_count, unsigned long long rec_capacity, int env_hits) {

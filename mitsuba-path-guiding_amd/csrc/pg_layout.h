@@ -59,6 +59,23 @@ struct GEnv {
 };
 static_assert(sizeof(GEnv) == 128, "GEnv layout");
 
+// Delta emitter record: 64 B (pg_set_delta_emitters; pg_capi.h pg_delta_emitter).  type: PG_EMITTER_*.  dir: the
+// spot's axis / the direction a directional light travels, unit length.  Spot: cos_cutoff, cos_beam and
+// inv_transition = 1 / (cutoff - beam) as SpotEmitter::configure precomputes them (spot.cpp:105-125).  Directional:
+// pos is the centre of the disk the light leaves from (bounding-sphere centre - dir * radius, directional.cpp:159-180)
+// and intensity the irradiance on a surface normal to dir.
+struct GDelta {
+    float pos[3];
+    uint32_t type;
+    float dir[3];
+    float cutoff;
+    float intensity[3];
+    float cos_cutoff;
+    float cos_beam, inv_transition;
+    float pad[2];
+};
+static_assert(sizeof(GDelta) == 64, "GDelta layout");
+
 // Texture record: 64 B (pg_set_textures; pg_capi.h pg_texture).  texels: width x height float4 (rgb, 0), row y at
 // texels + 4 * y * width; nullptr for a checkerboard.  mode: type | filter << 4 | wrap_u << 8 | wrap_v << 12.
 struct GTex {
@@ -546,4 +563,7 @@ struct GParams {
     // thin lens (pg_set_lens): world-space aperture radius, 0 = pinhole (the lens kernels are not launched), and
     // the distance of the focal plane along the viewing direction
     float lens_radius, focus_dist;
+    // the area emitters among num_emitters: emitter ei < num_area is sc.ems[ei], the delta emitters
+    // (pg_set_delta_emitters) follow as sc.delta[ei - num_area], the environment emitter is last
+    uint32_t num_area;
 };

@@ -1239,11 +1239,17 @@ __device__ __forceinline__ f3 envSampleDirect(const GEnv &e, f3 ref, float sx, f
 // Scene::sampleEmitterDirect without the visibility test (scene.cpp:871-895 + area.cpp:158-171 +
 // shape.cpp:102-115 + trimesh.cpp:412-423 + triangle.cpp:24-45); returns radiance/pdf.  With an
 // environment emitter (sc.env; compiled in with ENV only), it is emitter g.num_emitters - 1.
-template <bool ENV = false>
+// DELTA compiles in the delta emitters (sc.delta, pg_set_delta_emitters): emitters [g.num_area, g.num_area + their
+// count), after the area emitters and before the environment emitter.  Their samples are in the discrete measure
+// (*discrete = true): the pdf is the emitter-pick probability alone and the caller gives them MIS weight 1
+// (progressive_path.cpp:211: bsdfPdf = 0 unless the emitter is on a surface and the measure is the solid angle).
+template <bool ENV = false, bool DELTA = false>
 __device__ __forceinline__ f3 sampleEmitter(const GParams &g, const SceneDev &sc, f3 ref, f3 refN, float sx, float sy,
-                                            f3 &dOut, float &dist, float &pdfOut, f3 *pOut = nullptr) {
+                                            f3 &dOut, float &dist, float &pdfOut, f3 *pOut = nullptr,
+                                            bool *discrete = nullptr) {
     uint32_t ne = g.num_emitters;
     pdfOut = 0;
+    if (DELTA && discrete) *discrete = false;
     if (ne == 0) return mk1(0.f);
     uint32_t ei = min((uint32_t)(sx * (float)ne), ne - 1);
     sx = sx * (float)ne - (float)ei;
@@ -1255,6 +1261,37 @@ __device__ __forceinline__ f3 sampleEmitter(const GParams &g, const SceneDev &sc
         pdfOut = pdf * emPdf;
         if (pOut) *pOut = ref + dOut * dist;
         return v / emPdf;
+    }
+    if (DELTA && ei >= g.num_area) {
+#pragma clang fp contract(off)
+        const GDelta dl = sc.delta[ei - g.num_area];
+        const f3 pos = mk(dl.pos[0], dl.pos[1], dl.pos[2]), axis = mk(dl.dir[0], dl.dir[1], dl.dir[2]);
+        f3 value = mk(dl.intensity[0], dl.intensity[1], dl.intensity[2]);
+        if (dl.type == PG_EMITTER_DIRECTIONAL) {  // DirectionalEmitter::sampleDirect (directional.cpp:159-180)
+            const float distance = dot(ref - pos, axis);
+            if (distance < 0) return mk1(0.f);
+            dOut = -axis;
+            dist = distance;
+            if (pOut) *pOut = ref + dOut * dist;
+        } else {  // PointEmitter / SpotEmitter::sampleDirect (point.cpp:131-147, spot.cpp:184-200)
+            f3 d = pos - ref;
+            dist = sqrtf(dot(d, d));
+            const float inv = 1.0f / dist;
+            d = d * inv;
+            value = value * (inv * inv);
+            if (dl.type == PG_EMITTER_SPOT) {  // falloffCurve with a constant projection texture (spot.cpp:105-125)
+                const float cosTheta = dot(-d, axis);
+                if (cosTheta <= dl.cos_cutoff) return mk1(0.f);
+                if (cosTheta < dl.cos_beam) value = value * ((dl.cutoff - acosf(cosTheta)) * dl.inv_transition);
+            }
+            dOut = d;
+            if (pOut) *pOut = pos;
+        }
+        if (isZero(value)) return mk1(0.f);
+        const float emPdf = 1.0f / (float)ne;
+        pdfOut = emPdf;
+        if (discrete) *discrete = true;
+        return value / emPdf;
     }
     const GEmitter em = sc.ems[ei];
     // DiscreteDistribution::sampleReuse over the area CDF (lower_bound)

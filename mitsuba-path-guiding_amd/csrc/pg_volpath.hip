@@ -10,6 +10,7 @@
 // image is independent of which lane ran which item.  Random numbers: one sequential counter
 // stream per path (dimension 0 = pixel jitter, then one dimension per next1D / next2D), the same
 // stream the CPU oracle (oracle/orc_volpath.h) draws from.
+#include <type_traits>
 #include "pg_trace.h"
 
 // Index checks of the megakernel (debug build PG_VOL_CHECK=1, make volcheck): VCHK(cond, code, value)
@@ -695,7 +696,9 @@ __device__ __forceinline__ bool volRoulette(const GParams &g, VPath &P, VRng &rn
     P.scattered = true;
     return true;
 }
-template <bool GUIDED, bool SINK>
+// DELTA: delta emitters are set (pg_set_delta_emitters; SceneDev::delta): sampleEmitter's point / spot / directional
+// branches and the discrete-measure rule of the NEE; with DELTA = false none of it is compiled.
+template <bool GUIDED, bool SINK, bool DELTA = false>
 __device__ __forceinline__ bool volMedium(const GParams &g, const SceneDev &sc, const VolDev &v, const SDDev &sd,
                                           VPath &P, VRng &rng, const TStack &stk, uint32_t item, uint32_t &segs,
                                           uint32_t &shadows, f3 mp, VDefer &df, const VolWave &wk) {
@@ -726,13 +729,16 @@ __device__ __forceinline__ bool volMedium(const GParams &g, const SceneDev &sc, 
             rng.next2(s0, s1);
             f3 ep;
             float dist, pdf;
-            const f3 value = sampleEmitter(g, sc, mp, mk1(0.f), s0, s1, dD, dist, pdf, &ep);
+            bool discrete = false;  // a delta emitter's sample (pg_set_delta_emitters): MIS weight 1, no D-tree pdf
+            const f3 value = sampleEmitter<false, DELTA>(g, sc, mp, mk1(0.f), s0, s1, dD, dist, pdf, &ep, &discrete);
             if (pdf != 0) {
                 shadows++;
                 const float phaseVal = hgEval(hg, wi, dD);
                 if (phaseVal != 0 && !isZero(value)) {
                     deferNeeWalk<SINK>(df, wk, item, mp, ep, false, P.medium, maxInter, ndim);
-                    if (guiding) {
+                    if (DELTA && discrete) {
+                        deferNeeC<SINK>(df, wk, item, (P.T * value) * phaseVal);
+                    } else if (guiding) {
                         neeV = P.T * value;
                         neePdf = pdf;
                         neePhase = phaseVal;
@@ -797,7 +803,7 @@ __device__ __forceinline__ bool volMedium(const GParams &g, const SceneDev &sc, 
     return volRoulette(g, P, rng);
 }
 // MODELS: pg_device.h modelSel (-1 any material; PG_MODELS_DIFFUSE_NULL when the scene has only those)
-template <bool GUIDED, bool SINK, int MODELS = -1>
+template <bool GUIDED, bool SINK, int MODELS = -1, bool DELTA = false>
 __device__ __forceinline__ bool volSurface(const GParams &g, const SceneDev &sc, const VolDev &v, const SDDev &sd,
                                            VPath &P, VRng &rng, const TStack &stk, uint32_t item, uint32_t &segs,
                                            uint32_t &shadows, VDefer &df, const VolWave &wk) {
@@ -833,7 +839,8 @@ __device__ __forceinline__ bool volSurface(const GParams &g, const SceneDev &sc,
             rng.next2(s0, s1);
             f3 ep;
             float dist, pdf;
-            const f3 value = sampleEmitter(g, sc, h.p, refN, s0, s1, dD, dist, pdf, &ep);
+            bool discrete = false;  // a delta emitter's sample (pg_set_delta_emitters): MIS weight 1, no D-tree pdf
+            const f3 value = sampleEmitter<false, DELTA>(g, sc, h.p, refN, s0, s1, dD, dist, pdf, &ep, &discrete);
             if (pdf != 0) {
                 const int m2 = tm ? targetMedium(tm, dD, h.geoN) : P.medium;
                 shadows++;
@@ -843,7 +850,9 @@ __device__ __forceinline__ bool volSurface(const GParams &g, const SceneDev &sc,
                     if (!isZero(f) && (!g.strict_normals || dot(h.geoN, dD) * woL.z > 0)) {
                         const float bp = bsdfPdf<MODELS>(M, h.wi, woL);
                         deferNeeWalk<SINK>(df, wk, item, h.p, ep, true, m2, maxInter, ndim);
-                        if (guide) {
+                        if (DELTA && discrete) {
+                            deferNeeC<SINK>(df, wk, item, (P.T * value) * f);
+                        } else if (guide) {
                             neeV = (P.T * value) * f;
                             neePdf = pdf;
                             neeBp = bp;
@@ -982,7 +991,7 @@ __device__ __forceinline__ void clearDefer(VDefer &df) {
     df.k = -1;
 }
 
-template <bool GUIDED, int MODELS = -1>
+template <bool GUIDED, int MODELS = -1, bool DELTA = false>
 __device__ __forceinline__ bool volStep(const GParams &g, const SceneDev &sc, const VolDev &v, const SDDev &sd,
                                         VPath &P, VRng &rng, const TStack &stk, uint32_t item, uint32_t &segs,
                                         uint32_t &shadows, VDefer &df) {
@@ -990,18 +999,18 @@ __device__ __forceinline__ bool volStep(const GParams &g, const SceneDev &sc, co
     f3 mp = mk1(0.f);
     const VolWave none{};
     if (P.medium >= 0 && volFlight<GUIDED>(v, sd, P, rng, mp))
-        return volMedium<GUIDED, false>(g, sc, v, sd, P, rng, stk, item, segs, shadows, mp, df, none);
-    return volSurface<GUIDED, false, MODELS>(g, sc, v, sd, P, rng, stk, item, segs, shadows, df, none);
+        return volMedium<GUIDED, false, DELTA>(g, sc, v, sd, P, rng, stk, item, segs, shadows, mp, df, none);
+    return volSurface<GUIDED, false, MODELS, DELTA>(g, sc, v, sd, P, rng, stk, item, segs, shadows, df, none);
 }
 // one step with its walks resolved right away (k_vtail, k_volpath): the same arithmetic as the wavefront's
 // k_vvertex + k_vnee
-template <bool GUIDED, int MODELS = -1>
+template <bool GUIDED, int MODELS = -1, bool DELTA = false>
 __device__ __forceinline__ bool volStepResolved(const GParams &g, const SceneDev &sc, const VolDev &v, const SDDev &sd,
                                                 VPath &P, VRng &rng, const TStack &stk, uint32_t item, uint32_t &segs,
                                                 uint32_t &shadows) {
     VDefer df;
     clearDefer(df);
-    const bool alive = volStep<GUIDED, MODELS>(g, sc, v, sd, P, rng, stk, item, segs, shadows, df);
+    const bool alive = volStep<GUIDED, MODELS, DELTA>(g, sc, v, sd, P, rng, stk, item, segs, shadows, df);
     if (df.hit || df.nee) resolveDeferred(sc, v, df, rng.key, rng.sample, item, P.L, stk, segs, rng.lookups);
     return alive;
 }
@@ -1300,7 +1309,7 @@ struct VVertexWaves {
                                            : (KIND == 1 || KIND == 3 ? (NEE_STAGE ? PG_VSURFACE_WAVES : PG_VSURFACE_INLINE_WAVES)
                                                         : PG_VVERTEX_WAVES);
 };
-template <bool GUIDED, bool NEE_STAGE, int KIND>
+template <bool GUIDED, bool NEE_STAGE, int KIND, bool DELTA = false>
 __global__ __launch_bounds__(TRACE_BLOCK, (VVertexWaves<NEE_STAGE, KIND>::value)) void k_vvertex(GParams g, SceneDev sc, VolDev v, SDDev sd,
                                                                        VolWave w, Queue qm, Queue qs, Queue qd,
                                                                        uint32_t mblocks, uint32_t dblocks, Queue nf,
@@ -1331,9 +1340,9 @@ __global__ __launch_bounds__(TRACE_BLOCK, (VVertexWaves<NEE_STAGE, KIND>::value)
             clearDefer(df);
             bool alive;
             if (KIND == 0 || (KIND == 2 && medium))
-                alive = volMedium<GUIDED, NEE_STAGE>(g, sc, v, sd, P, rng, stk, slot, segs, shadows, xyz(w.mp[slot]), df, w);
+                alive = volMedium<GUIDED, NEE_STAGE, DELTA>(g, sc, v, sd, P, rng, stk, slot, segs, shadows, xyz(w.mp[slot]), df, w);
             else
-                alive = volSurface<GUIDED, NEE_STAGE, KIND == 3 ? PG_MODELS_DIFFUSE_NULL : -1>(g, sc, v, sd, P, rng, stk,
+                alive = volSurface<GUIDED, NEE_STAGE, KIND == 3 ? PG_MODELS_DIFFUSE_NULL : -1, DELTA>(g, sc, v, sd, P, rng, stk,
                                                                                           slot, segs, shadows, df, w);
             vertices++;
             const bool ended = !(alive && volDepthOk(g, P));
@@ -1410,7 +1419,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, PG_VNEE_WAVES) void k_vnee(GParams g, 
 #ifndef PG_VTAIL_WAVES
 #define PG_VTAIL_WAVES 3  // C5 442.3 / 441.9 against 439.2 / 439.6 at 2 (profiles/r05q_vol_waves/)
 #endif
-template <bool GUIDED, int MODELS>
+template <bool GUIDED, int MODELS, bool DELTA = false>
 __global__ __launch_bounds__(TRACE_BLOCK, PG_VTAIL_WAVES) void k_vtail(GParams g, SceneDev sc, VolDev v, SDDev sd,
                                                                      VolWave w, Queue qf, Queue qs, Queue qd,
                                                                      uint32_t fblocks, uint32_t dblocks) {
@@ -1433,10 +1442,10 @@ __global__ __launch_bounds__(TRACE_BLOCK, PG_VTAIL_WAVES) void k_vtail(GParams g
         if (!flight) {
             VDefer df;
             clearDefer(df);
-            alive = volSurface<GUIDED, false, MODELS>(g, sc, v, sd, P, rng, stk, slot, segs, shadows, df, w);
+            alive = volSurface<GUIDED, false, MODELS, DELTA>(g, sc, v, sd, P, rng, stk, slot, segs, shadows, df, w);
             if (df.hit || df.nee) resolveDeferred(sc, v, df, rng.key, rng.sample, slot, P.L, stk, segs, rng.lookups);
         }
-        while (alive) alive = volStepResolved<GUIDED, MODELS>(g, sc, v, sd, P, rng, stk, slot, segs, shadows);
+        while (alive) alive = volStepResolved<GUIDED, MODELS, DELTA>(g, sc, v, sd, P, rng, stk, slot, segs, shadows);
         volEnd(v, slot, P, rng, lookups);
     }
     volStats(v, segs, shadows, lookups);
@@ -1492,7 +1501,7 @@ int pg_launch_vol_vertex(hipStream_t s, const GParams &g, const SceneDev &sc, co
     const char *se = std::getenv("PG_VOL_SPLIT_VERTEX");
     const bool split = se && *se ? std::atoi(se) != 0 : true;
 #define PG_VV(GU, NS, KIND, ROWS, MB)                                                                                \
-    hipLaunchKernelGGL((k_vvertex<GU, NS, KIND>), dim3(PG_QSHARDS * (ROWS)), dim3(TRACE_BLOCK), 0, s, g, sc, v, sd, w, \
+    hipLaunchKernelGGL((k_vvertex<GU, NS, KIND, DE>), dim3(PG_QSHARDS * (ROWS)), dim3(TRACE_BLOCK), 0, s, g, sc, v, sd, w, \
                        med, surf, dsurf, MB, PG_QSHARDS * dr, next_flight, next_surf, next_dsurf, qn)
 #define PG_VV_ALL(GU, NS)                                                                                            \
     if (!split) {                                                                                                    \
@@ -1502,11 +1511,17 @@ int pg_launch_vol_vertex(hipStream_t s, const GParams &g, const SceneDev &sc, co
         if (dr + sr && v.models) PG_VV(GU, NS, 3, dr + sr, 0u);                                                      \
         else if (dr + sr) PG_VV(GU, NS, 1, dr + sr, 0u);                                                             \
     }
-    if (g.guiding) {
-        if (nee) { PG_VV_ALL(true, true) } else { PG_VV_ALL(true, false) }
-    } else {
-        if (nee) { PG_VV_ALL(false, true) } else { PG_VV_ALL(false, false) }
-    }
+    // sc.delta: delta emitters are set (pg_set_delta_emitters); scenes without them launch the kernels they always did
+    auto launch = [&](auto de) {
+        constexpr bool DE = decltype(de)::value;
+        if (g.guiding) {
+            if (nee) { PG_VV_ALL(true, true) } else { PG_VV_ALL(true, false) }
+        } else {
+            if (nee) { PG_VV_ALL(false, true) } else { PG_VV_ALL(false, false) }
+        }
+    };
+    if (sc.delta) launch(std::true_type{});
+    else launch(std::false_type{});
 #undef PG_VV_ALL
 #undef PG_VV
     return split ? (mr ? 1 : 0) + (dr + sr ? 1 : 0) : 1;  // kernels launched (bench.py's per-launch averages)
@@ -1530,20 +1545,25 @@ void pg_launch_vol_tail(hipStream_t s, const GParams &g, const SceneDev &sc, con
     if (fr + sr + dr == 0) return;
     const dim3 grid(PG_QSHARDS * (fr + dr + sr));
 #define PG_VT(GU, MO)                                                                                                \
-    hipLaunchKernelGGL((k_vtail<GU, MO>), grid, dim3(TRACE_BLOCK), 0, s, g, sc, v, sd, w, flight, surf, dsurf,      \
+    hipLaunchKernelGGL((k_vtail<GU, MO, DE>), grid, dim3(TRACE_BLOCK), 0, s, g, sc, v, sd, w, flight, surf, dsurf,      \
                        PG_QSHARDS * fr, PG_QSHARDS * dr)
-    if (g.guiding) {
-        if (v.models) PG_VT(true, PG_MODELS_DIFFUSE_NULL); else PG_VT(true, -1);
-    } else {
-        if (v.models) PG_VT(false, PG_MODELS_DIFFUSE_NULL); else PG_VT(false, -1);
-    }
+    auto launch = [&](auto de) {  // sc.delta: the instantiations with the delta emitters' NEE compiled in
+        constexpr bool DE = decltype(de)::value;
+        if (g.guiding) {
+            if (v.models) PG_VT(true, PG_MODELS_DIFFUSE_NULL); else PG_VT(true, -1);
+        } else {
+            if (v.models) PG_VT(false, PG_MODELS_DIFFUSE_NULL); else PG_VT(false, -1);
+        }
+    };
+    if (sc.delta) launch(std::true_type{});
+    else launch(std::false_type{});
 #undef PG_VT
 }
 
 namespace {
 }  // namespace
 
-template <bool GUIDED, bool LENS>
+template <bool GUIDED, bool LENS, bool DELTA = false>
 __global__ __launch_bounds__(VOL_BLOCK, PG_VOL_WAVES) void k_volpath(GParams g, SceneDev sc, VolDev v, SDDev sd,
                                                        const uint32_t *__restrict__ local_pixels, uint32_t pix_begin,
                                                        uint32_t npix, uint32_t nlayers, uint32_t sample_base) {
@@ -1577,7 +1597,7 @@ __global__ __launch_bounds__(VOL_BLOCK, PG_VOL_WAVES) void k_volpath(GParams g, 
             }
         }
         if (!__any(alive)) break;
-        if (alive && !volStepResolved<GUIDED>(g, sc, v, sd, P, rng, stk, item, segs, shadows)) {
+        if (alive && !volStepResolved<GUIDED, -1, DELTA>(g, sc, v, sd, P, rng, stk, item, segs, shadows)) {
 #if PG_VOL_CHECK
             if (VCHK(item < nitems, 3, item))
 #endif
@@ -1707,12 +1727,17 @@ void pg_launch_volpath(hipStream_t s, const GParams &g, const SceneDev &sc, cons
     const uint64_t want = (n + VOL_BLOCK - 1) / VOL_BLOCK;
     const uint32_t grid = (uint32_t)(want < TRACE_MAX_BLOCKS ? want : TRACE_MAX_BLOCKS);
 #define PG_VP(G, L)                                                                                              \
-    hipLaunchKernelGGL((k_volpath<G, L>), dim3(grid), dim3(VOL_BLOCK), 0, s, g, sc, v, sd, local_pixels, pix_begin, \
+    hipLaunchKernelGGL((k_volpath<G, L, DE>), dim3(grid), dim3(VOL_BLOCK), 0, s, g, sc, v, sd, local_pixels, pix_begin, \
                        npix, nlayers, sample_base)
-    if (g.lens_radius > 0) {  // a thin lens (pg_set_lens); off: the kernels as they were
-        if (g.guiding) PG_VP(true, true); else PG_VP(false, true);
-    } else {
-        if (g.guiding) PG_VP(true, false); else PG_VP(false, false);
-    }
+    auto launch = [&](auto de) {  // sc.delta: the instantiations with the delta emitters' NEE compiled in
+        constexpr bool DE = decltype(de)::value;
+        if (g.lens_radius > 0) {  // a thin lens (pg_set_lens); off: the kernels as they were
+            if (g.guiding) PG_VP(true, true); else PG_VP(false, true);
+        } else {
+            if (g.guiding) PG_VP(true, false); else PG_VP(false, false);
+        }
+    };
+    if (sc.delta) launch(std::true_type{});
+    else launch(std::false_type{});
 #undef PG_VP
 }

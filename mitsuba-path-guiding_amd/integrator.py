@@ -124,6 +124,28 @@ class Device:
             self.set_textures(scene.textures, scene.texture_bindings, scene.texcoords)
         if getattr(scene, "lens", None):  # pg_upload_scene turned the lens off: its camera is a pinhole
             self.set_lens(*scene.lens)
+        if getattr(scene, "delta_emitters", None):  # pg_upload_scene cleared any delta emitters of an earlier scene
+            self.set_delta_emitters(scene.delta_emitters)
+
+    def set_delta_emitters(self, emitters):
+        """pg_set_delta_emitters: point, spot and directional lights (pg_delta_emitter records, scenes.point_light /
+        spot_light / directional_light) of the uploaded scene, picked after its area emitters.  After upload, before
+        the first render pass; an empty list removes them."""
+        emitters = list(emitters)
+        arr = (capi.pg_delta_emitter * max(1, len(emitters)))(*emitters)
+        self._chk(self.lib.pg_set_delta_emitters(self.h, arr, len(emitters)))
+
+    def emitter_query(self, ref, samples):
+        """pg_emitter_query: the shaders' emitter sampling over the scene's area, delta and environment emitters at
+        ref (n, 3) with a zero reference normal and samples (n, 2) -> (n, 8): d, dist, value / pdf (rgb), measure
+        (0 failed, 1 solid angle, 2 discrete)."""
+        ref = np.ascontiguousarray(ref, np.float32).reshape(-1, 3)
+        samples = np.ascontiguousarray(samples, np.float32).reshape(-1, 2)
+        if len(ref) != len(samples):
+            raise ValueError("emitter_query: one sample per reference point")
+        out = np.zeros((len(ref), 8), np.float32)
+        self._chk(self.lib.pg_emitter_query(self.h, _p(ref), _p(samples), len(ref), _p(out)))
+        return out
 
     def set_lens(self, aperture_radius, focus_distance=0.0):
         """pg_set_lens: a thin lens of world-space radius `aperture_radius` focused at `focus_distance` along the

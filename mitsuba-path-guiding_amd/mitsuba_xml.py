@@ -28,7 +28,9 @@ adapter's flatten() produces from Scene::getShapes()/getBSDFs() (INTEGRATION.md)
                     rectangle, cube, disk and sphere (tessellated), with
                     toWorld, flipNormals, faceNormals, a nested or referenced bsdf and an area emitter
   emitter           area (in a shape), envmap (.npy / .pfm / uncompressed or zlib EXR), constant
-                    (as a uniform envmap)
+                    (as a uniform envmap); point (position or toWorld), spot (toWorld, cutoffAngle, beamWidth;
+                    no projection texture) and directional (direction or toWorld), each with its intensity /
+                    irradiance given and samplingWeight 1, recorded as Scene.delta_emitters
   medium            homogeneous (sigmaS / sigmaA or sigmaT / albedo, scale, g; grey sigmaT) with an hg or
                     isotropic phase, declared at the top level or nested in a shape, attached to
                     shapes as <ref name="interior|exterior">; a shape without a BSDF is a null
@@ -531,8 +533,40 @@ class _Loader:
         elif typ == "constant":  # src/emitters/constant.cpp: uniform radiance, sampled through the envmap CDFs
             rad = np.asarray(P.get("radiance", np.ones(3)), np.float32).reshape(-1)
             self.sc.set_envmap(np.ones((16, 32, 3), np.float32) * (rad if rad.size == 3 else rad[0]), to_world=R)
+        elif typ in ("point", "spot", "directional"):
+            self.delta_emitter(el, typ, P)
         else:
-            self.unsupported("emitter", typ, "only area (in a shape), envmap and constant emitters")
+            self.unsupported("emitter", typ, "only area (in a shape), point, spot, directional, envmap and constant "
+                                             "emitters")
+
+    def delta_emitter(self, el, typ, P):
+        """<emitter type="point" | "spot" | "directional"> (src/emitters/point.cpp, spot.cpp, directional.cpp)"""
+        tag = f"<emitter type=\"{typ}\">"
+        if float(P.get("samplingWeight", 1.0)) != 1.0:
+            raise NotImplementedError(f"{tag}: samplingWeight other than 1 (emitters are picked uniformly)")
+        if typ == "spot" and any(c.tag == "texture" or (c.tag == "ref" and c.get("name") == "texture") for c in el):
+            raise NotImplementedError(f"{tag}: texture (the projection texture is not supported)")
+        power = "irradiance" if typ == "directional" else "intensity"
+        if power not in P:
+            raise NotImplementedError(f"{tag}: {power} is required (the D65 default spectrum is not restated)")
+        value = np.asarray(P[power], np.float64).reshape(-1)
+        M = P.get("toWorld", np.eye(4))
+        if typ == "point":
+            if "position" in P and "toWorld" in P:
+                raise ValueError(f"{tag}: only one of position and toWorld can be given (point.cpp:66-69)")
+            pos = P["position"] if "position" in P else M[:3, 3]
+            self.sc.add_point_light(tuple(np.asarray(pos, np.float64).tolist()), value)
+        elif typ == "spot":
+            cutoff = float(P.get("cutoffAngle", 20.0))
+            beam = float(P.get("beamWidth", cutoff * 3.0 / 4.0))
+            o = M[:3, 3]
+            axis = M[:3, :3] @ [0, 0, 1]
+            self.sc.add_spot_light(tuple(o.tolist()), None, value, cutoff, beam, direction=tuple(axis.tolist()))
+        else:
+            if "direction" in P and "toWorld" in P:
+                raise ValueError(f"{tag}: only one of direction and toWorld can be given (directional.cpp:72-75)")
+            d = P["direction"] if "direction" in P else M[:3, :3] @ [0, 0, 1]
+            self.sc.add_directional_light(tuple(np.asarray(d, np.float64).tolist()), value)
 
     def sensor(self, el):
         typ = self.attr(el, "type")
@@ -1066,6 +1100,30 @@ def _bsdf_xml(m, tex=None):
     return inner
 
 
+def _delta_emitter_xml(e):
+    """<emitter> element of a pg_delta_emitter (point: position; spot: toWorld with the axis as its +z column, angles
+    in degrees; directional: direction)"""
+    f32l = lambda a: [float(np.float32(x)) for x in a]
+    xyz = lambda a: f'x="{a[0]!r}" y="{a[1]!r}" z="{a[2]!r}"'
+    if e.type == capi.PG_EMITTER_POINT:
+        return (f'<emitter type="point"><point name="position" {xyz(f32l(e.position))}/>'
+                f'{_rgb_el("intensity", f32l(e.intensity))}</emitter>')
+    if e.type == capi.PG_EMITTER_DIRECTIONAL:
+        return (f'<emitter type="directional"><vector name="direction" {xyz(f32l(e.direction))}/>'
+                f'{_rgb_el("irradiance", f32l(e.intensity))}</emitter>')
+    a = np.asarray(f32l(e.direction), np.float64)
+    n = a / np.linalg.norm(a)
+    s = np.cross(n, [1.0, 0, 0] if abs(n[0]) < 0.9 else [0, 1.0, 0])
+    s /= np.linalg.norm(s)
+    M = np.eye(4)
+    M[:3, 0], M[:3, 1], M[:3, 2], M[:3, 3] = s, np.cross(n, s), a, f32l(e.position)
+    deg = lambda r: float(np.degrees(np.float64(np.float32(r))))
+    return (f'<emitter type="spot">{_rgb_el("intensity", f32l(e.intensity))}'
+            f'<float name="cutoffAngle" value="{deg(e.cutoff_angle)!r}"/><float name="beamWidth" value="{deg(e.beam_width)!r}"/>'
+            f'<transform name="toWorld"><matrix value="{" ".join(repr(float(x)) for x in M.reshape(-1))}"/>'
+            f'</transform></emitter>')
+
+
 def save(scene, path, spp=64, integrator="path"):
     """Write `scene` as a Mitsuba 0.5 scene: one OBJ per shape (positions, normals), inline BSDFs,
     area emitters, the perspective sensor (lookat + fov along x; thinlens with apertureRadius and focusDistance
@@ -1145,6 +1203,8 @@ def save(scene, path, spp=64, integrator="path"):
                    f'<float name="scale" value="{float(np.float32(sc.envmap.scale))!r}"/>'
                    f'<transform name="toWorld"><matrix value="{" ".join(repr(float(x)) for x in M.reshape(-1))}"/>'
                    f'</transform></emitter>')
+    for e in getattr(sc, "delta_emitters", []):
+        out.append(_delta_emitter_xml(e))
     out.append("</scene>")
     with open(path, "w") as f:
         f.write("\n".join(out) + "\n")

@@ -100,6 +100,8 @@ class Scene:
         self.texture_bindings = []
         # thin lens (pg_set_lens): (aperture radius, focus distance), or None: the pinhole of `camera`
         self.lens = None
+        # delta emitters (pg_set_delta_emitters): pg_delta_emitter records, picked after the area emitters
+        self.delta_emitters = []
 
     # -- construction
     def add_material(self, m):
@@ -213,6 +215,24 @@ class Scene:
             raise ValueError("set_lens: need a finite aperture radius >= 0 and, with a lens, a focus distance > 0")
         self.lens = (r, f) if r > 0 else None
 
+    def add_point_light(self, position, intensity):
+        """Point emitter (src/emitters/point.cpp): `intensity` in W/sr, a scalar or rgb.  The device wrapper sets the
+        scene's delta emitters after every upload (pg_set_delta_emitters)."""
+        self.delta_emitters.append(point_light(position, intensity))
+        return len(self.delta_emitters) - 1
+
+    def add_spot_light(self, position, target, intensity, cutoff_angle=20, beam_width=None, direction=None):
+        """Spot emitter (src/emitters/spot.cpp) at `position` shining towards `target`; angles in degrees, the beam
+        width defaults to 3/4 of the cutoff angle (spot.cpp:70-71).  No projection texture."""
+        self.delta_emitters.append(spot_light(position, target, intensity, cutoff_angle, beam_width, direction))
+        return len(self.delta_emitters) - 1
+
+    def add_directional_light(self, direction, irradiance):
+        """Directional emitter (src/emitters/directional.cpp): `direction` the light travels in, `irradiance` on a
+        surface normal to it."""
+        self.delta_emitters.append(directional_light(direction, irradiance))
+        return len(self.delta_emitters) - 1
+
     def finalize(self):
         self.positions = np.ascontiguousarray(np.concatenate(self._pos), np.float32)
         self.normals = np.ascontiguousarray(np.concatenate(self._nrm), np.float32)
@@ -261,6 +281,59 @@ class Scene:
     def bounds(self):
         p = self.positions
         return p.min(0), p.max(0)
+
+
+def _rgb3(v):
+    v = np.asarray(v, np.float32).reshape(-1)
+    if v.size == 1:
+        v = np.repeat(v, 3)
+    if v.size != 3 or not np.all(np.isfinite(v)) or np.any(v < 0):
+        raise ValueError("a light's intensity is a finite scalar or rgb >= 0")
+    return (C.c_float * 3)(*v.tolist())
+
+
+def point_light(position, intensity):
+    """pg_delta_emitter of a point emitter."""
+    e = capi.pg_delta_emitter()
+    e.type = capi.PG_EMITTER_POINT
+    e.position = (C.c_float * 3)(*[float(x) for x in position])
+    e.intensity = _rgb3(intensity)
+    return e
+
+
+def spot_light(position, target, intensity, cutoff_angle=20, beam_width=None, direction=None):
+    """pg_delta_emitter of a spot emitter; angles in degrees, beam width 3/4 of the cutoff by default.  `direction`
+    (with target=None) gives the axis itself instead of a point it passes through."""
+    cutoff = float(cutoff_angle)
+    beam = cutoff * 3.0 / 4.0 if beam_width is None else float(beam_width)
+    if not 0 <= beam < cutoff < 180:
+        raise ValueError("spot light: need 0 <= beam_width < cutoff_angle < 180 degrees")
+    if (target is None) == (direction is None):
+        raise ValueError("spot light: give either a target or a direction")
+    axis = (np.asarray(direction, np.float64).reshape(3) if target is None
+            else np.asarray(target, np.float64) - np.asarray(position, np.float64))
+    if not np.linalg.norm(axis) > 0:
+        raise ValueError("spot light: zero axis (position and target coincide)")
+    e = capi.pg_delta_emitter()
+    e.type = capi.PG_EMITTER_SPOT
+    e.position = (C.c_float * 3)(*[float(x) for x in position])
+    e.direction = (C.c_float * 3)(*axis.tolist())  # pg_set_delta_emitters normalises it
+    e.intensity = _rgb3(intensity)
+    e.cutoff_angle = np.deg2rad(cutoff)
+    e.beam_width = np.deg2rad(beam)
+    return e
+
+
+def directional_light(direction, irradiance):
+    """pg_delta_emitter of a directional emitter."""
+    d = np.asarray(direction, np.float64).reshape(3)
+    if not np.linalg.norm(d) > 0:
+        raise ValueError("directional light: zero direction")
+    e = capi.pg_delta_emitter()
+    e.type = capi.PG_EMITTER_DIRECTIONAL
+    e.direction = (C.c_float * 3)(*d.tolist())  # pg_set_delta_emitters normalises it
+    e.intensity = _rgb3(irradiance)
+    return e
 
 
 _TEX_FILTERS = {"nearest": capi.PG_TEXFILTER_NEAREST, "bilinear": capi.PG_TEXFILTER_BILINEAR}
@@ -409,9 +482,10 @@ def cylinder(center, radius, height, n=64):
 
 # ---------------------------------------------------------------------------------------------
 # C1/C2: the Cornell box (measured geometry of the Cornell data set, in metres)
-def cornell(width=512, height=512, short_material=None, tall_material=None):
+def cornell(width=512, height=512, short_material=None, tall_material=None, area_light=True):
     """Cornell box (C1/C2).  short_material / tall_material: optional pg_material for the blocks
-    (default: the white diffuse)."""
+    (default: the white diffuse).  area_light=False leaves the ceiling panel out (a box lit by delta emitters
+    alone); the caller then adds lights (Scene.add_point_light, ...), which the device wrapper reads at upload."""
     s = Scene()
     s.name = "cornell"
     white = s.add_material(material("diffuse", reflectance=(0.725, 0.71, 0.68)))
@@ -435,7 +509,8 @@ def cornell(width=512, height=512, short_material=None, tall_material=None):
     # light (slightly below the ceiling), facing down
     V, F = quad(P(343.0, 548.7, 227.0), P(343.0, 548.7, 332.0), P(213.0, 548.7, 332.0), P(213.0, 548.7, 227.0),
                 facing=(0, -1, 0))
-    s.add_mesh(V, F, material=light, radiance=(17.0, 12.0, 4.0))
+    if area_light:
+        s.add_mesh(V, F, material=light, radiance=(17.0, 12.0, 4.0))
 
     def block(quads, m):
         pts = np.array([p for q in quads for p in q], np.float32)

@@ -129,6 +129,9 @@ public:
                                   (uint32_t) m_flat.bindings.size(), m_flat.hasUV ? m_flat.uv.data() : NULL));
         // the thinlens sensor's aperture and focal plane (flatten); the upload left the pinhole
         if (m_flat.lensRadius > 0) check(pg_set_lens(m_ctx, m_flat.lensRadius, m_flat.focusDistance));
+        // point, spot and directional emitters (flattenDeltaEmitters); after the upload, before any pass
+        if (!m_flat.deltas.empty())
+            check(pg_set_delta_emitters(m_ctx, m_flat.deltas.data(), (uint32_t) m_flat.deltas.size()));
         // the film's reconstruction filter: any separable filter through its own discretised table
         // (rfilter.h:76-77); the box keeps the per-pixel film
         const ReconstructionFilter *rf = scene->getSensor()->getFilm()->getReconstructionFilter();
@@ -405,6 +408,7 @@ protected:
         bool hasUV = false;
         bool mirrorX = false, hasEnv = false;
         float lensRadius = 0, focusDistance = 0;  // the thinlens sensor (pg_set_lens); radius 0: a pinhole
+        std::vector<pg_delta_emitter> deltas;     // point, spot and directional emitters (pg_set_delta_emitters)
         void bind() {  // pg_upload_scene copies everything; the arrays live until then
             desc.num_vertices = (uint32_t) (pos.size() / 3);
             desc.num_triangles = (uint32_t) (idx.size() / 3);
@@ -430,6 +434,7 @@ protected:
                         Flattened &f) const;
     pg_material material(const BSDF *bsdf) const;
     void flattenEnvironment(const Scene *scene, Flattened &f) const;
+    void flattenDeltaEmitters(const Scene *scene, Flattened &f) const;
     int32_t flattenMedium(const Medium *medium, const AABB &bounds, Flattened &f,
                           std::map<const Medium *, int32_t> &index) const;
 
@@ -597,6 +602,53 @@ inline void GuidedGPUIntegrator::flattenTexture(const BSDF *bsdf, uint32_t mater
     b.material = material;
     b.texture = texIndex[tex.get()];
     f.bindings.push_back(b);
+}
+
+// The delta emitters (pg_set_delta_emitters): PointEmitter (point.cpp), SpotEmitter (spot.cpp) and DirectionalEmitter
+// (directional.cpp) by their world transform at t = 0 and their properties.  The library picks emitters uniformly, so
+// a sampling weight other than 1 is an error, as is every emitter it has no model for (collimated, sky, sun, sunsky):
+// it would be left out of the image without a word.  A spot's projection texture attached as a child object is not
+// visible from here; one given as a property is rejected.
+inline void GuidedGPUIntegrator::flattenDeltaEmitters(const Scene *scene, Flattened &f) const {
+    const ref_vector<Emitter> &ems = scene->getEmitters();
+    for (size_t i = 0; i < ems.size(); ++i) {
+        const Emitter *em = ems[i].get();
+        if (em->isOnSurface() || em->isEnvironmentEmitter()) continue;  // area emitters and the environment map
+        const std::string cls = em->getClass()->getName();
+        const Properties &p = em->getProperties();
+        if (em->getSamplingWeight() != 1)
+            Log(EError, "guided_gpu: emitter %s: a samplingWeight other than 1 is not supported", cls.c_str());
+        const Transform T = em->getWorldTransform()->eval(0);
+        const Point o = T(Point(0.0f));
+        const Vector z = T(Vector(0, 0, 1));
+        pg_delta_emitter e;
+        memset(&e, 0, sizeof(e));
+        float rgb[4] = {0, 0, 0, 0};
+        for (int a = 0; a < 3; ++a) {
+            e.position[a] = (float) o[a];
+            e.direction[a] = (float) z[a];
+        }
+        if (cls == "PointEmitter") {
+            e.type = PG_EMITTER_POINT;
+            pgRGB(p.getSpectrum("intensity", Spectrum::getD65()), rgb);
+        } else if (cls == "SpotEmitter") {
+            if (p.hasProperty("texture"))
+                Log(EError, "guided_gpu: the spot emitter's projection texture is not supported");
+            e.type = PG_EMITTER_SPOT;
+            pgRGB(p.getSpectrum("intensity", Spectrum(1.0f)), rgb);
+            const Float cutoff = p.getFloat("cutoffAngle", 20);
+            e.cutoff_angle = (float) degToRad(cutoff);
+            e.beam_width = (float) degToRad(p.getFloat("beamWidth", cutoff * 3.0f / 4.0f));
+        } else if (cls == "DirectionalEmitter") {
+            e.type = PG_EMITTER_DIRECTIONAL;
+            pgRGB(p.getSpectrum("irradiance", Spectrum::getD65()), rgb);
+        } else {
+            Log(EError, "guided_gpu: emitter %s is not supported (area, point, spot, directional, envmap and constant "
+                "are)", cls.c_str());
+        }
+        for (int a = 0; a < 3; ++a) e.intensity[a] = rgb[a];
+        f.deltas.push_back(e);
+    }
 }
 
 inline void GuidedGPUIntegrator::flattenEnvironment(const Scene *scene, Flattened &f) const {
@@ -805,6 +857,7 @@ inline GuidedGPUIntegrator::Flattened GuidedGPUIntegrator::flatten(const Scene *
     }
     f.desc.camera_medium = mediumOf(cam->getMedium());
     flattenEnvironment(scene, f);
+    flattenDeltaEmitters(scene, f);
     return f;  // the caller binds the descriptor's pointers (Flattened::bind) to its own copy
 }
 
