@@ -183,52 +183,8 @@ static void buildBinary(const float *P, const uint32_t *I, uint32_t nt, uint32_t
     }
 }
 
-// Woop unit-triangle record (3 x float4) of triangle t: rows of the inverse of [e0 e1 n] in double.
-static void woopRecord(const float *P, const uint32_t *I, uint32_t t, float *w) {
-    const float *v0 = P + 3 * (size_t)I[3 * (size_t)t], *v1 = P + 3 * (size_t)I[3 * (size_t)t + 1],
-                *v2 = P + 3 * (size_t)I[3 * (size_t)t + 2];
-    double e0[3], e1[3], n[3];
-    for (int a = 0; a < 3; ++a) {
-        e0[a] = (double)v0[a] - v2[a];
-        e1[a] = (double)v1[a] - v2[a];
-    }
-    n[0] = e0[1] * e1[2] - e0[2] * e1[1];
-    n[1] = e0[2] * e1[0] - e0[0] * e1[2];
-    n[2] = e0[0] * e1[1] - e0[1] * e1[0];
-    // M = [e0 e1 n] (columns); rows of M^-1 map (p - v2) -> (a, b, c)
-    double m[3][3] = {{e0[0], e1[0], n[0]}, {e0[1], e1[1], n[1]}, {e0[2], e1[2], n[2]}};
-    double det = m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) - m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0]) +
-                 m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]);
-    for (int k = 0; k < 12; ++k) w[k] = 0.0f;
-    if (!(std::fabs(det) > 0) || !std::isfinite(det)) return;  // degenerate: never hit (NaN t)
-    double inv[3][3];
-    inv[0][0] = (m[1][1] * m[2][2] - m[1][2] * m[2][1]) / det;
-    inv[0][1] = (m[0][2] * m[2][1] - m[0][1] * m[2][2]) / det;
-    inv[0][2] = (m[0][1] * m[1][2] - m[0][2] * m[1][1]) / det;
-    inv[1][0] = (m[1][2] * m[2][0] - m[1][0] * m[2][2]) / det;
-    inv[1][1] = (m[0][0] * m[2][2] - m[0][2] * m[2][0]) / det;
-    inv[1][2] = (m[0][2] * m[1][0] - m[0][0] * m[1][2]) / det;
-    inv[2][0] = (m[1][0] * m[2][1] - m[1][1] * m[2][0]) / det;
-    inv[2][1] = (m[0][1] * m[2][0] - m[0][0] * m[2][1]) / det;
-    inv[2][2] = (m[0][0] * m[1][1] - m[0][1] * m[1][0]) / det;
-    auto rowdot = [&](int r) { return inv[r][0] * v2[0] + inv[r][1] * v2[1] + inv[r][2] * v2[2]; };
-    // w0: c(p) = r2.p - r2.v2 ; stored as (r2, r2.v2) so that t = (w0.w - r2.o) / r2.d
-    w[0] = (float)inv[2][0];
-    w[1] = (float)inv[2][1];
-    w[2] = (float)inv[2][2];
-    w[3] = (float)rowdot(2);
-    w[4] = (float)inv[0][0];
-    w[5] = (float)inv[0][1];
-    w[6] = (float)inv[0][2];
-    w[7] = (float)(-rowdot(0));
-    w[8] = (float)inv[1][0];
-    w[9] = (float)inv[1][1];
-    w[10] = (float)inv[1][2];
-    w[11] = (float)(-rowdot(1));
-}
-
 // TriAccel record of triangle t (TriAccel::load, triaccel.h:37-94, in fp32 as the reference computes
-// it; this file builds with -ffp-contract=off): 12 floats, pg_layout.h PG_TRIACCEL
+// it; this file builds with -ffp-contract=off): 12 floats, pg_layout.h "Triangle records"
 static void triAccelRecord(const float *P, const uint32_t *I, uint32_t t, float *w) {
     static const int waldModulo[4] = {1, 2, 0, 1};
     const float *A = P + 3 * (size_t)I[3 * (size_t)t], *B = P + 3 * (size_t)I[3 * (size_t)t + 1],
@@ -480,86 +436,16 @@ static bool buildWide(const float *P, const uint32_t *I, uint32_t nt, uint32_t s
     out.tris.assign(4 * (size_t)PG_TRI_F4(nt), 0.0f);
     for (uint32_t k = 0; k < nt; ++k) {
         float rec[12];
-        (PG_TRIACCEL ? triAccelRecord : woopRecord)(P, I, out.order[k], rec);
+        triAccelRecord(P, I, out.order[k], rec);
         for (uint32_t r = 0; r < 3; ++r) std::memcpy(&out.tris[4 * (size_t)PG_TRI_ROW(k, r)], rec + 4 * r, 16);
     }
     return true;
 }
 
-// binary BVH (for closest-hit queries) over the same tree: nodes whose leaves index the shared
-// triangle order (posOf: a binary leaf's triangles lie inside one wide leaf slot, so they stay
-// contiguous)
-static bool buildBinaryBvh(const std::vector<BNode> &bn, uint32_t maxDepth, const std::vector<uint32_t> &posOf,
-                           uint32_t stack_limit, BvhOut &out) {
-    out.max_depth = maxDepth;
-    if (maxDepth + 1 > stack_limit) return false;
-    // ---- pack: the inner nodes of the top PG_BVH_TOP_LEVELS levels first, breadth first (k_trace
-    // stages them in LDS), then the rest depth first; a leaf root gets a synthetic parent
-    std::vector<int32_t> gpuIndex(bn.size(), -1);
-    std::vector<int32_t> innerOrder;
-    {
-        std::vector<std::pair<int32_t, int>> level{{0, 0}};
-        std::vector<int32_t> frontier;  // children below the top levels, left to right
-        for (size_t k = 0; k < level.size(); ++k) {
-            const auto [n, d] = level[k];
-            if (bn[n].leaf) continue;
-            if (d >= PG_BVH_TOP_LEVELS) {
-                frontier.push_back(n);
-                continue;
-            }
-            gpuIndex[n] = (int32_t)innerOrder.size();
-            innerOrder.push_back(n);
-            level.push_back({bn[n].child[0], d + 1});
-            level.push_back({bn[n].child[1], d + 1});
-        }
-        out.top_nodes = (uint32_t)innerOrder.size();
-        std::vector<int32_t> s(frontier.rbegin(), frontier.rend());
-        while (!s.empty()) {
-            int32_t n = s.back();
-            s.pop_back();
-            if (bn[n].leaf) continue;
-            gpuIndex[n] = (int32_t)innerOrder.size();
-            innerOrder.push_back(n);
-            s.push_back(bn[n].child[1]);
-            s.push_back(bn[n].child[0]);
-        }
-    }
-    auto ref = [&](int32_t n) -> int32_t {
-        if (bn[n].leaf) return (int32_t)(~((posOf[bn[n].first] << 4) | bn[n].count));
-        return gpuIndex[n];
-    };
-    auto putNode = [&](float *o, const Box &b0, int32_t r0, const Box &b1, int32_t r1) {
-        o[0] = b0.lo[0]; o[1] = b0.hi[0]; o[2] = b0.lo[1]; o[3] = b0.hi[1];
-        o[4] = b1.lo[0]; o[5] = b1.hi[0]; o[6] = b1.lo[1]; o[7] = b1.hi[1];
-        o[8] = b0.lo[2]; o[9] = b0.hi[2]; o[10] = b1.lo[2]; o[11] = b1.hi[2];
-        std::memcpy(&o[12], &r0, 4);
-        std::memcpy(&o[13], &r1, 4);
-        o[14] = 0;
-        o[15] = 0;
-    };
-    if (innerOrder.empty()) {  // the root is a leaf: synthetic inner root + empty far-away leaf
-        out.nodes.assign(16, 0.0f);
-        Box far;
-        for (int a = 0; a < 3; ++a) far.lo[a] = far.hi[a] = 1e30f;
-        int32_t empty = (int32_t)(~0u << 4);  // ~((0 << 4) | 0) with count 0
-        empty = ~(int32_t)0;                  // first 0, count 0
-        putNode(&out.nodes[0], bn[0].box, ref(0), far, empty);
-        out.top_nodes = 1;
-        return true;
-    }
-    out.nodes.assign(16 * innerOrder.size(), 0.0f);
-    for (size_t i = 0; i < innerOrder.size(); ++i) {
-        const BNode &n = bn[innerOrder[i]];
-        putNode(&out.nodes[16 * i], bn[n.child[0]].box, ref(n.child[0]), bn[n.child[1]].box, ref(n.child[1]));
-    }
-    return true;
-}
-
 // one 4-wide node (pg_layout.h PG_QNODE_*): child boxes box[2a][s] / box[2a+1][s] (lo / hi along axis
-// a) of the first `used` slots, refs r[4]; full-precision planes, or (PG_QNODE_QUANT) bytes in the
+// a) of the first `used` slots, refs r[4]; the planes as bytes in the
 // node's frame rounded outward as the 8-wide nodes' are
 static void putQuadNode(float *o, const float box[6][4], const int32_t r[4], int used) {
-#if PG_QNODE_QUANT
     Box parent;
     if (used == 0)
         for (int a = 0; a < 3; ++a) parent.lo[a] = parent.hi[a] = 0.0f;
@@ -592,15 +478,9 @@ static void putQuadNode(float *o, const float box[6][4], const int32_t r[4], int
     std::memcpy(&o[4], r, 16);
     std::memcpy(&o[8], w, 24);
     o[14] = o[15] = 0.0f;
-#else
-    (void)used;
-    for (int a = 0; a < 6; ++a)
-        for (int s = 0; s < 4; ++s) o[4 * a + s] = box[a][s];
-    std::memcpy(&o[24], r, 16);
-#endif
 }
 
-// 4-wide BVH (PG_BVH4, closest hit) over the same tree; its leaves are the binary leaves (same refs).
+// 4-wide BVH (closest hit) over the same tree; its leaves are the binary leaves (same refs).
 // Which binary nodes a 4-wide node absorbs is the SAH-optimal choice (the 8-wide collapse's dynamic
 // programme with 4 slots and the leaves fixed: it minimises the summed surface area of the opened
 // nodes, i.e. the expected node visits); PG_BVH4_GREEDY=1 opens the largest-area inner child
@@ -700,7 +580,7 @@ static bool buildQuadBvh(const std::vector<BNode> &bn, const std::vector<uint32_
         return true;
     }
     // the top PG_BVH4_TOP_LEVELS levels' nodes are processed breadth first, so their children -- the
-    // nodes of depths <= PG_BVH4_TOP_LEVELS -- take the first indices (k_rays' LDS tile); the rest depth
+    // nodes of depths <= PG_BVH4_TOP_LEVELS -- take the first indices; the rest depth
     // first.  Node contents and refs do not depend on the order: walks return the same hits.
     std::vector<QTask> bfs{{0, alloc(), 1}};
     std::vector<uint32_t> depthOf{0};
@@ -768,19 +648,11 @@ static bool buildQuadBvh(const std::vector<BNode> &bn, const std::vector<uint32_
 }
 
 bool buildBvh(const float *P, const uint32_t *I, uint32_t nt, uint32_t stack_limit, BvhOut &out) {
-    if (nt == 0) {  // every ray misses: an inner root with two empty far-away leaves; a childless wide node
-        out.nodes.assign(16, 0.0f);
-        for (int k = 0; k < 4; ++k) out.nodes[k] = out.nodes[4 + k] = 1e30f;
-        out.nodes[8] = out.nodes[9] = out.nodes[10] = out.nodes[11] = 1e30f;
-        int32_t empty = ~(int32_t)0;
-        std::memcpy(&out.nodes[12], &empty, 4);
-        std::memcpy(&out.nodes[13], &empty, 4);
-        if (PG_BVH4) {  // one node without children
-            out.nodes.assign(4 * PG_QNODE_F4, 0.0f);
-            const int32_t r[4] = {PG_QNODE_EMPTY, PG_QNODE_EMPTY, PG_QNODE_EMPTY, PG_QNODE_EMPTY};
-            const float box[6][4] = {};
-            putQuadNode(out.nodes.data(), box, r, 0);
-        }
+    if (nt == 0) {  // every ray misses: a 4-wide node without children; a childless wide node
+        out.nodes.assign(4 * PG_QNODE_F4, 0.0f);
+        const int32_t r[4] = {PG_QNODE_EMPTY, PG_QNODE_EMPTY, PG_QNODE_EMPTY, PG_QNODE_EMPTY};
+        const float box[6][4] = {};
+        putQuadNode(out.nodes.data(), box, r, 0);
         out.wnodes.assign(PG_WIDE_NODE_F4 * 4, 0.0f);
         out.order.clear();
         out.tris.clear();
@@ -801,11 +673,8 @@ bool buildBvh(const float *P, const uint32_t *I, uint32_t nt, uint32_t stack_lim
         out.hi[a] = all.hi[a];
     }
     if (!buildWide(P, I, nt, stack_limit, bn, ord, out, posOf)) return false;
-    if (PG_BVH4) {
-        out.max_depth = maxDepth;
-        return buildQuadBvh(bn, posOf, out);
-    }
-    return buildBinaryBvh(bn, maxDepth, posOf, stack_limit, out);
+    out.max_depth = maxDepth;
+    return buildQuadBvh(bn, posOf, out);
 }
 
 }  // namespace pgh

@@ -8,22 +8,18 @@
 // for positive normal arguments and equals (float)log((double)x) on every tracking argument and on
 // 22 M sampled positive floats (same file).
 //
-// The tracking loops (heterogeneous.cpp:568,634) use `trackLog`: the device library's logf by default.
+// The tracking loops (heterogeneous.cpp:568,634) use `trackLog`: the device library's logf.
 // With fastlog there, C5 runs at 407 against 445 Mpaths/s (the FP64 temporaries push k_vflight from 0
 // to 68 B/lane of scratch and k_vvertex's surface launch from 156 to 304, profiles/r05x_fastlog/), while
 // the C5 image-level parity prints are the same with either (every smoke pixel within 1e-3 of the
 // oracle's, the same-tree renders 0.999 / 1.000, identical record counts): a tracking step's distance
 // differs by an ulp where the roundings differ, and paths almost never part ways over it.
-// PG_TRACK_FASTLOG=1 builds the tracking loops with fastlog (unit tests then match the oracle bit for bit).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
 // log(x) for float x, rounded to float exactly as (float)log((double)x) but for ties within ~2^-52
 __device__ __forceinline__ float fastlog(float x) {
-#if PG_FASTLOG_LIBM  // A/B: the device library's double log (tools/r05x_gpu.sh ab/dbl)
-    return (float)log((double)x);
-#endif
     // special arguments without the library call (whose inlined body would cost registers at every
     // call site): 0 -> -inf, negative / NaN -> NaN, +inf -> +inf; denormals are scaled by 2^23 (exact)
     if (!(x > 0.0f) || x == __int_as_float(0x7f800000)) return x == 0.0f ? -__int_as_float(0x7f800000) : x * (x > 0.0f ? 1.0f : __int_as_float(0x7fc00000));
@@ -59,14 +55,7 @@ __device__ __forceinline__ float fastlog(float x) {
 }
 __device__ __forceinline__ float fastexp(float x) { return (float)exp((double)x); }
 
-#ifndef PG_TRACK_FASTLOG
-#define PG_TRACK_FASTLOG 0
-#endif
 // the tracking loops' log(1 - u) (see above)
 __device__ __forceinline__ float trackLog(float x) {
-#if PG_TRACK_FASTLOG
-    return fastlog(x);
-#else
     return logf(x);
-#endif
 }

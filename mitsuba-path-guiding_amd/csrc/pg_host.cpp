@@ -214,7 +214,7 @@ struct Ctx {
     hipEvent_t vw_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // stage timing (kernel_timing)
     uint32_t vol_cap = 0;
     uint32_t num_tris = 0, num_mats = 0;
-    uint32_t bvh_top_nodes = 0;  // breadth-first top levels of the binary BVH (staged in LDS by k_trace)
+    uint32_t bvh_top_nodes = 0;  // breadth-first top levels of the 4-wide BVH (SceneDev::top_nodes: no reader)
     // padded boxes over the emitter triangles (pg_layout.h "Doom probe"): SceneDev::em_box
     uint32_t num_em_boxes = 0;
     float em_absmax = 0.0f;
@@ -1594,30 +1594,26 @@ pg_status pg_upload_scene(void *ctx, const pg_scene_desc *d) {
     if ((s = upload(c, c->rtab, rtab))) return s;
     for (auto &mo : rtabOf) c->host_mats[mo.first].rtrans = c->rtab.as<float>() + mo.second;
     c->base_mats = c->host_mats;
-    c->bvh_top_nodes = std::min<uint32_t>(bvh.top_nodes, PG_BVH4 ? PG_BVH4_TOP_NODES : PG_BVH_TOP_NODES);
+    c->bvh_top_nodes = std::min<uint32_t>(bvh.top_nodes, PG_BVH4_TOP_NODES);
     if ((s = upload(c, c->nodes, bvh.nodes)) || (s = upload(c, c->tris, bvh.tris)) ||
         (s = upload(c, c->wnodes, bvh.wnodes)) || (s = upload(c, c->tshade, shade)) ||
         (s = upload(c, c->tclass, tclass)) ||
         (s = upload(c, c->mats, c->host_mats)) || (s = upload(c, c->ems, ems)) || (s = upload(c, c->emtri, emtri)) ||
         (s = upload(c, c->emcdf, emcdf)) || (s = upload(c, c->tmed, tmed)) || (s = upload(c, c->tcheap, tcheap)))
         return s;
-    // densities: one buffer, each grid 256-B aligned (bricked, see pg_layout.h GMedium)
+    // densities: one buffer, each grid 256-B aligned (corner-packed, see pg_layout.h GMedium)
     {
         size_t words = 0, linMax = 0;
         std::vector<size_t> at;
-        std::vector<float> stage;
-        // corner-packed grids (pg_layout.h PG_DENSITY_CORNERS); a grid with a dimension of 1 has no
+        // corner-packed grids (pg_layout.h "Corner-packed density"); a grid with a dimension of 1 has no
         // cell (every lookup is 0) and keeps no density
         for (uint32_t m = 0; m < d->num_media; ++m) {
             const pg_medium &pm = d->media[m];
             at.push_back(words);
-            gmed[m].bx = (pm.res[0] + 3) / 4;
-            gmed[m].by = (pm.res[1] + 3) / 4;
             const size_t lin = (size_t)pm.res[0] * pm.res[1] * pm.res[2];
             const size_t cells = (size_t)(pm.res[0] - 1) * (pm.res[1] - 1) * (pm.res[2] - 1);
-            const size_t n = PG_DENSITY_BRICKS ? (size_t)gmed[m].bx * gmed[m].by * ((pm.res[2] + 3) / 4) * 64
-                             : PG_DENSITY_CORNERS ? cells * 8 : lin;
-            if (PG_DENSITY_CORNERS && cells) linMax = std::max(linMax, lin);
+            const size_t n = cells * 8;
+            if (cells) linMax = std::max(linMax, lin);
             words += (n + 63) & ~(size_t)63;
         }
         {
@@ -1625,8 +1621,7 @@ pg_status pg_upload_scene(void *ctx, const pg_scene_desc *d) {
             const hipError_t e = c->density.grow(std::max<size_t>(words * 4, 256));
             if (e != hipSuccess)
                 return fail(c, e == hipErrorOutOfMemory ? PG_ERR_OOM : PG_ERR_HIP,
-                            "pg_upload_scene: cannot allocate " + std::to_string(words * 4) + " B of density" +
-                                (PG_DENSITY_CORNERS ? " (corner-packed: 8 floats per cell)" : "") + ": " +
+                            "pg_upload_scene: cannot allocate " + std::to_string(words * 4) + " B of density (corner-packed: 8 floats per cell): " +
                                 hipGetErrorString(e));
         }
         DevBuf linTmp;  // the linear grid of a corner-packed medium, expanded on the device
@@ -1634,24 +1629,11 @@ pg_status pg_upload_scene(void *ctx, const pg_scene_desc *d) {
         for (uint32_t m = 0; m < d->num_media; ++m) {
             const pg_medium &pm = d->media[m];
             const size_t n = (size_t)pm.res[0] * pm.res[1] * pm.res[2];
-            if (PG_DENSITY_CORNERS) {
-                HIPC(c, hipMemcpyAsync(linTmp.p, pm.density, n * 4, hipMemcpyHostToDevice, c->stream));
-                pg_launch_density_corners(c->stream, linTmp.as<float>(), pm.res[0], pm.res[1], pm.res[2],
-                                          c->density.as<float>() + at[m]);
-                HIPC(c, hipGetLastError());
-                HIPC(c, hipStreamSynchronize(c->stream));  // linTmp is reused by the next medium
-            } else if (PG_DENSITY_BRICKS) {
-                const uint32_t bx = gmed[m].bx, by = gmed[m].by, bz = (pm.res[2] + 3) / 4;
-                stage.assign((size_t)bx * by * bz * 64, 0.0f);
-                for (uint32_t z = 0; z < pm.res[2]; ++z)
-                    for (uint32_t y = 0; y < pm.res[1]; ++y)
-                        for (uint32_t x = 0; x < pm.res[0]; ++x)
-                            stage[(((size_t)(z >> 2) * by + (y >> 2)) * bx + (x >> 2)) * 64 + (z & 3) * 16 + (y & 3) * 4 +
-                                  (x & 3)] = pm.density[((size_t)z * pm.res[1] + y) * pm.res[0] + x];
-                HIPC(c, hipMemcpy(c->density.as<float>() + at[m], stage.data(), stage.size() * 4, hipMemcpyHostToDevice));
-            } else {
-                HIPC(c, hipMemcpyAsync(c->density.as<float>() + at[m], pm.density, n * 4, hipMemcpyHostToDevice, c->stream));
-            }
+            HIPC(c, hipMemcpyAsync(linTmp.p, pm.density, n * 4, hipMemcpyHostToDevice, c->stream));
+            pg_launch_density_corners(c->stream, linTmp.as<float>(), pm.res[0], pm.res[1], pm.res[2],
+                                      c->density.as<float>() + at[m]);
+            HIPC(c, hipGetLastError());
+            HIPC(c, hipStreamSynchronize(c->stream));  // linTmp is reused by the next medium
             gmed[m].density = c->density.as<float>() + at[m];
         }
         // majorant grids (PG_MAJORANT_GRID tracking): one buffer, per-medium offsets

@@ -6,7 +6,7 @@
 #include "pg_layout.h"
 
 struct SceneDev {
-    const float4 *nodes;    // binary BVH (closest hit), PG_BVH_NODE_F4 float4 per node
+    const float4 *nodes;    // 4-wide BVH (closest hit), PG_QNODE_F4 float4 per node
     const float4 *tris;     // 3 float4 per BVH-order triangle
     const float4 *wnodes;   // 8-wide BVH (shadow rays), PG_WIDE_NODE_F4 float4 per node
     const float4 *wtris;    // the same triangle records as tris (both BVHs share one triangle order)
@@ -17,7 +17,7 @@ struct SceneDev {
     const float4 *emtri;    // PG_TRI_SHADE_F4 float4 per emitter triangle
     const float *emcdf;
     const GEnv *env;        // environment emitter (the last emitter), or nullptr
-    uint32_t top_nodes;     // binary-BVH nodes [0, top_nodes) are the top levels (k_trace stages them in LDS)
+    uint32_t top_nodes;     // 4-wide nodes [0, top_nodes) are the breadth-first top levels (no reader)
     // padded boxes over the emitter triangles (pg_layout.h "Doom probe"; by value, so they sit in scalar registers)
     uint32_t num_em_boxes;
     float em_absmax;        // the boxes' largest |coordinate|
@@ -262,7 +262,7 @@ void pg_launch_volpath(hipStream_t s, const GParams &g, const SceneDev &sc, cons
 void pg_launch_vol_camera(hipStream_t s, const GParams &g, const SceneDev &sc, const VolDev &v, const VolWave &w,
                           const uint32_t *local_pixels, uint32_t pix_begin, uint32_t npix, uint32_t nlayers,
                           uint32_t sample_base, Queue flight, Queue surf, Queue dsurf);
-// surf / dsurf: surface vertices on other / delta-class surfaces (and escaped rays), pg_volpath.hip PG_VOL_SPLIT_SURF
+// surf / dsurf: surface vertices on other / delta-class surfaces (and escaped rays), pg_volpath.hip cheapSurface
 void pg_launch_vol_flight(hipStream_t s, const GParams &g, const SceneDev &sc, const VolDev &v, const SDDev &sd,
                           const VolWave &w, Queue flight, uint32_t max_flight, Queue med, Queue surf, Queue dsurf);
 int pg_launch_vol_vertex(hipStream_t s, const GParams &g, const SceneDev &sc, const VolDev &v, const SDDev &sd,
@@ -276,7 +276,7 @@ void pg_launch_vol_tail(hipStream_t s, const GParams &g, const SceneDev &sc, con
                         uint32_t max_dsurf);
 void pg_launch_phase_query(hipStream_t s, const GMedium *medium, const float *in, const float *wog, uint32_t n,
                            float *out);
-// corner-packed density of a linear grid (pg_layout.h PG_DENSITY_CORNERS); out: 8 floats per cell
+// corner-packed density of a linear grid (pg_layout.h "Corner-packed density"); out: 8 floats per cell
 void pg_launch_density_corners(hipStream_t s, const float *lin, uint32_t rx, uint32_t ry, uint32_t rz, float *out);
 void pg_launch_medium_query(hipStream_t s, const GMedium *medium, int op, const float *in, const uint32_t *keys,
                             uint32_t n, float *out);

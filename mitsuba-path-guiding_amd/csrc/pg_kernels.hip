@@ -11,25 +11,11 @@
 
 #include "pg_trace.h"
 
-// LDS staging of node and material tiles (measured, off by default: profiles/r02k_lds_ab/ -- C3
-// within noise to -1 %: the top BVH levels and the few materials already hit in L1, and the block
+// LDS staging of material tiles (measured, off by default: profiles/r02k_lds_ab/ -- C3
+// within noise to -1 %: the few materials already hit in L1, and the block
 // fill + barrier is paid by every short-lived shading block)
 #ifndef SHADE_LDS_MATS
 #define SHADE_LDS_MATS 0   // > 0: k_shade stages up to this many materials in LDS (64 = 8 KiB)
-#endif
-#ifndef PG_RAYS_LDS_TOP
-#define PG_RAYS_LDS_TOP 0  // 1: k_rays' closest-hit blocks stage the 4-wide BVH's top levels in LDS (1.3 KiB)
-#endif
-// the LDS tile of the closest-hit BVH's top levels: node size and capacity of this build's BVH
-#if PG_BVH4
-#define PG_TOP_NODE_F4 PG_QNODE_F4
-#define PG_TOP_TILE_F4 (PG_BVH4_TOP_NODES * PG_QNODE_F4)
-#else
-#define PG_TOP_NODE_F4 PG_BVH_NODE_F4
-#define PG_TOP_TILE_F4 (PG_BVH_TOP_NODES * PG_BVH_NODE_F4)
-#endif
-#ifndef PG_TRACE_LDS_TOP
-#define PG_TRACE_LDS_TOP 0  // 1: k_trace stages the BVH's top PG_BVH_TOP_LEVELS levels in LDS (2 KiB)
 #endif
 
 // =============================================================================================
@@ -172,17 +158,10 @@ __device__ __forceinline__ void classAppend(int cls, uint32_t slot, const ClassQ
 // CAM: the rows are camera rays (the chunk's first launch), whose tmin / tmax are in the rows; bounce rays otherwise
 // first: the camera rays' bounce with denoiser features on (pg_config.aovs): the hit record of every
 // path also goes to p.aov, which k_film resolves into albedo and normal (nullptr: off)
-// WIDE (PG_CLOSEST_WIDE, A/B): the closest hits walk the shadow rays' 8-wide quantised BVH (octant order,
-// boxes culled at tmax; no slab padding) instead of the 4-wide nodes: k_rays 29.4 against 23.9 ms per
-// calibration pass, C3 549-553 against 616-621 Mpaths/s (profiles/r05ag_closest_wide/): octant order
-// visits more boxes than the 4-wide walk's sorted descent saves in node fetches
-#ifndef PG_CLOSEST_WIDE
-#define PG_CLOSEST_WIDE 0
-#endif
-template <bool ENV, bool LTOP, bool CAM, bool WIDE = false>
+template <bool ENV, bool CAM>
 __device__ __forceinline__ void traceRows(const GParams &g, const SceneDev &sc, const PathDev &p, const Queue &q,
                                           const ClassQueues &cqs, float4 *first, uint32_t bid, uint32_t nblk,
-                                          const TStack &stk, const float4 *top, int ntop) {
+                                          const TStack &stk) {
     const uint32_t s = bid & (PG_QSHARDS - 1);
     const uint32_t n = q.counts[s];
     const uint32_t *items = q.items + (size_t)s * q.stride;
@@ -201,12 +180,7 @@ __device__ __forceinline__ void traceRows(const GParams &g, const SceneDev &sc, 
             float tmax = CAM ? d.w : __builtin_huge_valf();
             uint32_t tri = 0xFFFFFFFFu;
             float u = 0, v = 0;
-            bool h;
-            if constexpr (WIDE)
-                h = traverseWide<false>(sc.wnodes, sc.wtris, xyz(o), xyz(d), tmin, tmax, tri, u, v,
-                                        WStack{stk.lds, stk.ovf, stk.ostride});
-            else
-                h = traverse<false, LTOP>(sc.nodes, sc.tris, xyz(o), xyz(d), tmin, tmax, tri, u, v, stk, top, ntop);
+            const bool h = traverse<false>(sc.nodes, sc.tris, xyz(o), xyz(d), tmin, tmax, tri, u, v, stk);
             const bool doomed = (slot >> 31) != 0;
             slot &= 0x7FFFFFFFu;
             float4 hr = make_float4(h ? tmax : 0.0f, __uint_as_float(h ? tri : 0xFFFFFFFFu), u, v);
@@ -222,148 +196,11 @@ __device__ __forceinline__ void traceRows(const GParams &g, const SceneDev &sc, 
     }
 }
 
-// traceRows with persistent lanes (PG_TRACE_PERSIST, A/B, off): each wave takes a contiguous segment of its
-// shard's queue and runs the closest-hit walk one while-while round at a time (pg_trace.h Walk4); once at least
-// PG_TRACE_REFILL of its 64 lanes have finished their rays, they take the segment's next rays together (a lane
-// refill costs the whole wave the ray loads and the walk setup, so refills are batched, as k_volpath's).  A
-// finished lane writes its hit record and joins the class append of that round.  Every ray's walk is traverse4's,
-// so hits, films and trees are the grid-stride kernel's bit for bit (tests/test_gpu_parity.py, _configs, _params:
-// 90/90 with it on).  Measured slower (profiles/r06_persist/): C3 521-523 against 637 Mpaths/s, k_rays 31.6 against
-// 22.6 ms and k_shade_all 26.7 against 22.2 ms per calibration pass.  With 8 waves per SIMD the idle lanes of one
-// wave's while-while rounds are already covered by the other waves' issue, so the refill rounds only add their
-// ballots and setup; and the class queues come out in completion order instead of queue order, which costs the
-// shading kernel its ray coherence (6 waves per SIMD: 559-561, k_rays 27.0 ms).
-#ifndef PG_TRACE_PERSIST
-#define PG_TRACE_PERSIST 0
-#endif
-#ifndef PG_TRACE_REFILL
-#define PG_TRACE_REFILL 24
-#endif
-template <bool ENV>
-__device__ __forceinline__ void traceRowsPersist(const GParams &g, const SceneDev &sc, const PathDev &p, const Queue &q,
-                                                 const ClassQueues &cqs, float4 *first, uint32_t bid, uint32_t nblk,
-                                                 const TStack &stk) {
-    const uint32_t s = bid & (PG_QSHARDS - 1);
-    const uint32_t n = q.counts[s];
-    const uint32_t *items = q.items + (size_t)s * q.stride;
-    constexpr uint32_t kWavesPerBlock = TRACE_BLOCK / 64;
-    const uint32_t waves = (nblk / PG_QSHARDS) * kWavesPerBlock;
-    const uint32_t wv = (bid / PG_QSHARDS) * kWavesPerBlock + threadIdx.x / 64;
-    const uint32_t per = (n + waves - 1) / waves;
-    uint32_t cur = min(n, wv * per);
-    const uint32_t end = min(n, cur + per);
-    const int lane = threadIdx.x & 63;
-    bool active = false, doomed = false;
-    uint32_t slot = 0;
-    float woPdf = 0.0f;
-    Walk4 w;
-    for (;;) {
-        const unsigned long long act = __ballot(active);
-        const uint32_t idle = 64u - (uint32_t)__popcll(act);
-        if (cur < end && (idle >= PG_TRACE_REFILL || act == 0)) {  // batched refill of the idle lanes
-            const uint32_t rank = (uint32_t)__popcll(~act & ((1ull << lane) - 1ull));
-            if (!active && cur + rank < end) {
-                slot = items[cur + rank];
-                const float4 o = ldS(&p.ray_o[slot]), d = ldS(&p.ray_d[slot]);
-                doomed = rayDoomed(o);
-                woPdf = d.w;
-                walk4Start(w, xyz(o), xyz(d), fabsf(o.w), __builtin_huge_valf());
-                active = true;
-            }
-            cur += min(idle, end - cur);
-        }
-        if (__ballot(active) == 0) break;  // the segment is done (a refill above found no ray left)
-        bool fin = false;
-        if (active) fin = walk4Round(w, sc.nodes, sc.tris, stk);
-        int cls = -1;
-        if (fin) {
-            const bool h = w.hitTri != 0xFFFFFFFFu;
-            float4 hr = make_float4(h ? w.tmax : 0.0f, __uint_as_float(h ? w.hitTri : 0xFFFFFFFFu), w.hu, w.hv);
-            if (first) first[slot] = hr;
-            if (ENV && !h) {
-                const f3 e = envEscapeRadiance(g, sc, p, slot, w.d, p.pinfo[slot].z, woPdf);
-                hr = make_float4(e.x, hr.y, e.y, e.z);
-            }
-            cls = hitClass(sc, h, w.hitTri, doomed, hr);
-            stS(&p.hit[slot], hr);
-            active = false;
-        }
-        classAppend(cls, slot, cqs, s);
-    }
-}
-
-// traceRows with two rays per lane (PG_TRACE_PAIR, A/B): a block's grid-stride step takes 2 x TRACE_BLOCK rows
-// of its shard, lane t rows base + t and base + TRACE_BLOCK + t, and walks both at once (pg_trace.h walk4Pair),
-// so each lane has two rays' node fetches in flight; both class appends follow in row order.  The second
-// walk's stack is a second LDS column block and a second band of the overflow ring (kPairRing rows on).
-#ifndef PG_TRACE_PAIR
-#define PG_TRACE_PAIR 0
-#endif
-constexpr uint32_t kPairRing = PG_QSTACK_DEPTH - LDS_STACK;
-template <bool ENV>
-__device__ __forceinline__ void finishWalk(const GParams &g, const SceneDev &sc, const PathDev &p, const Walk4 &w,
-                                           uint32_t slot, bool doomed, float woPdf, float4 *first, int &cls) {
-    const bool h = w.hitTri != 0xFFFFFFFFu;
-    float4 hr = make_float4(h ? w.tmax : 0.0f, __uint_as_float(h ? w.hitTri : 0xFFFFFFFFu), w.hu, w.hv);
-    if (first) first[slot] = hr;
-    if (ENV && !h) {
-        const f3 e = envEscapeRadiance(g, sc, p, slot, w.d, p.pinfo[slot].z, woPdf);
-        hr = make_float4(e.x, hr.y, e.y, e.z);
-    }
-    cls = hitClass(sc, h, w.hitTri, doomed, hr);
-    stS(&p.hit[slot], hr);
-}
-template <bool ENV>
-__device__ __forceinline__ void traceRowsPair(const GParams &g, const SceneDev &sc, const PathDev &p, const Queue &q,
-                                              const ClassQueues &cqs, float4 *first, uint32_t bid, uint32_t nblk,
-                                              const TStack &sa, const TStack &sb) {
-    const uint32_t s = bid & (PG_QSHARDS - 1);
-    const uint32_t n = q.counts[s];
-    const uint32_t *items = q.items + (size_t)s * q.stride;
-    for (uint32_t base = (bid / PG_QSHARDS) * 2 * TRACE_BLOCK; base < n; base += nblk / PG_QSHARDS * 2 * TRACE_BLOCK) {
-        const uint32_t ia = base + threadIdx.x, ib = ia + TRACE_BLOCK;
-        uint32_t slotA = 0, slotB = 0;
-        bool doomedA = false, doomedB = false;
-        float woPdfA = 0.0f, woPdfB = 0.0f;
-        Walk4 a, b;
-        walk4Idle(a);
-        walk4Idle(b);
-        if (ia < n) {
-            slotA = items[ia];
-            const float4 o = ldS(&p.ray_o[slotA]), d = ldS(&p.ray_d[slotA]);
-            doomedA = rayDoomed(o);
-            woPdfA = d.w;
-            walk4Start(a, xyz(o), xyz(d), fabsf(o.w), __builtin_huge_valf());
-        }
-        if (ib < n) {
-            slotB = items[ib];
-            const float4 o = ldS(&p.ray_o[slotB]), d = ldS(&p.ray_d[slotB]);
-            doomedB = rayDoomed(o);
-            woPdfB = d.w;
-            walk4Start(b, xyz(o), xyz(d), fabsf(o.w), __builtin_huge_valf());
-        }
-        walk4Pair(a, b, sc.nodes, sc.tris, sa, sb);
-        int ca = -1, cb = -1;
-        if (ia < n) finishWalk<ENV>(g, sc, p, a, slotA, doomedA, woPdfA, first, ca);
-        if (ib < n) finishWalk<ENV>(g, sc, p, b, slotB, doomedB, woPdfB, first, cb);
-        classAppend(ca, slotA, cqs, s);
-        classAppend(cb, slotB, cqs, s);
-    }
-}
-
 template <bool ENV, bool CAM>
 __global__ __launch_bounds__(TRACE_BLOCK) void k_trace(GParams g, SceneDev sc, PathDev p, Queue q, ClassQueues cqs,
                                                        float4 *first) {
     __shared__ uint32_t stack[LDS_STACK * TRACE_BLOCK];
-    // the BVH's top levels (breadth first, pg_layout.h PG_BVH_TOP_NODES), staged in LDS once per block
-    __shared__ float4 top[(PG_TRACE_LDS_TOP ? PG_TOP_TILE_F4 : 1)];
-    const int ntop = PG_TRACE_LDS_TOP ? (int)sc.top_nodes : 0;
-    if (PG_TRACE_LDS_TOP) {
-        for (uint32_t k = threadIdx.x; k < (uint32_t)ntop * PG_TOP_NODE_F4; k += TRACE_BLOCK) top[k] = sc.nodes[k];
-        __syncthreads();
-    }
-    traceRows<ENV, PG_TRACE_LDS_TOP != 0, CAM>(g, sc, p, q, cqs, first, blockIdx.x, gridDim.x, threadStack(stack, p.stack_ovf),
-                                          top, ntop);
+    traceRows<ENV, CAM>(g, sc, p, q, cqs, first, blockIdx.x, gridDim.x, threadStack(stack, p.stack_ovf));
 }
 
 // shadow-ray mint at the shading point o (the extension ray's origin): Epsilon * max |o_i|
@@ -477,9 +314,6 @@ __global__ __launch_bounds__(TRACE_BLOCK) void k_probe(SceneDev sc, PathDev p, Q
 // blocks of their own, so they do not lengthen the closest-hit waves.  All parts are grid-stride loops over their
 // shards; the overflow ring holds three launches' worth of threads (3 x pg_stack_overflow_words(0)).
 static_assert(2 * WIDE_LDS_STACK >= LDS_STACK, "k_rays / k_trace_rays share one LDS stack array");
-#ifndef PG_RAYS_TRACE_FIRST
-#define PG_RAYS_TRACE_FIRST 1
-#endif
 #ifndef PG_RAYS_WAVES
 #define PG_RAYS_WAVES 8
 #endif
@@ -487,43 +321,20 @@ static_assert(2 * WIDE_LDS_STACK >= LDS_STACK, "k_rays / k_trace_rays share one 
 template <bool ENV, bool COUNT = false>
 __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PG_RAYS_WAVES))) void k_rays(GParams g, SceneDev sc, PathDev p, Queue q, ClassQueues cqs,
                                                       Queue shq, uint32_t shadow_blocks, Queue pq, uint32_t probe_blocks) {
-    // >= LDS_STACK words per thread (twice that for the paired walks)
-    __shared__ uint32_t stack[(PG_TRACE_PAIR ? 2 : 1) * 2 * WIDE_LDS_STACK * TRACE_BLOCK];
-    // the probe blocks come last in either order
+    // >= LDS_STACK words per thread
+    __shared__ uint32_t stack[2 * WIDE_LDS_STACK * TRACE_BLOCK];
+    // the probe blocks come last
     if (blockIdx.x >= gridDim.x - probe_blocks) {
         probeRows(sc, p, pq, cqs, blockIdx.x - (gridDim.x - probe_blocks), probe_blocks, threadStack(stack, p.stack_ovf));
         return;
     }
-#if PG_RAYS_TRACE_FIRST  // the costlier closest-hit blocks dispatched first (profiles/r03zg_rays_order_ab)
     const uint32_t trace_blocks = gridDim.x - probe_blocks - shadow_blocks;
     if (blockIdx.x >= trace_blocks) {
         shadowRows<COUNT>(sc, p, shq, blockIdx.x - trace_blocks, shadow_blocks, threadWideStack(stack, p.stack_ovf));
     } else {
-        // the 4-wide BVH's breadth-first top levels in LDS (PG_RAYS_LDS_TOP, A/B; round 5 re-measure of the
-        // round-2 tile on the 64-B nodes)
-        __shared__ float4 top[PG_RAYS_LDS_TOP ? PG_TOP_TILE_F4 : 1];
-        const int ntop = PG_RAYS_LDS_TOP ? (int)sc.top_nodes : 0;
-        if (PG_RAYS_LDS_TOP) {
-            for (uint32_t k = threadIdx.x; k < (uint32_t)ntop * PG_TOP_NODE_F4; k += TRACE_BLOCK) top[k] = sc.nodes[k];
-            __syncthreads();
-        }
         const TStack sa = threadStack(stack, p.stack_ovf);
-        if (PG_TRACE_PAIR && !PG_RAYS_LDS_TOP && !PG_CLOSEST_WIDE && PG_BVH4 && PG_QNODE_QUANT)
-            traceRowsPair<ENV>(g, sc, p, q, cqs, nullptr, blockIdx.x, trace_blocks, sa,
-                               TStack{sa.lds + LDS_STACK * TRACE_BLOCK, sa.ovf + (size_t)kPairRing * sa.ostride, sa.ostride});
-        else if (PG_TRACE_PERSIST && !PG_RAYS_LDS_TOP && !PG_CLOSEST_WIDE && PG_BVH4 && PG_QNODE_QUANT)
-            traceRowsPersist<ENV>(g, sc, p, q, cqs, nullptr, blockIdx.x, trace_blocks, sa);
-        else
-            traceRows<ENV, PG_RAYS_LDS_TOP != 0, false, PG_CLOSEST_WIDE != 0>(g, sc, p, q, cqs, nullptr, blockIdx.x, trace_blocks,
-                                                 sa, top, ntop);
+        traceRows<ENV, false>(g, sc, p, q, cqs, nullptr, blockIdx.x, trace_blocks, sa);
     }
-#else
-    if (blockIdx.x < shadow_blocks)
-        shadowRows<COUNT>(sc, p, shq, blockIdx.x, shadow_blocks, threadWideStack(stack, p.stack_ovf));
-    else
-        traceRows<ENV, false, false>(g, sc, p, q, cqs, nullptr, blockIdx.x - shadow_blocks,
-                              gridDim.x - probe_blocks - shadow_blocks, threadStack(stack, p.stack_ovf), nullptr, 0);
-#endif
 }
 
 // ray order key of a new extension ray (PG_RAY_SORT): direction octant, then the Morton code of the
@@ -540,16 +351,6 @@ __device__ __forceinline__ uint32_t rayOrderKey(const SDDev &sd, f3 o, f3 d) {
     return (oct << 9) | m;
 }
 
-// PG_SD_PREFETCH (round 6): shadeOne issues the guided lookup's jump-grid and leaf-record loads from the ray's
-// o + t d before the hit triangle and material resolve (the exact position decides; identical results)
-#ifndef PG_SD_PREFETCH
-#define PG_SD_PREFETCH 0
-#endif
-// PG_MAT_UNIFORM (round 6, A/B): shadeOne loads its material record once per distinct material of the wave, at a
-// wave-uniform address (readfirstlane waterfall), instead of as a per-lane gather
-#ifndef PG_MAT_UNIFORM
-#define PG_MAT_UNIFORM 0
-#endif
 // one bounce of Li for every queued path (progressive_path.cpp:149-306 + guiding)
 // MODEL >= 0 compiles only that BSDF model's code (material-class queues filled by k_trace);
 // CAN_GUIDE = false drops the SD-tree code for classes that are never guided (delta lobes).
@@ -652,24 +453,8 @@ __device__ __forceinline__ void shadeOne(const GParams &g, const SceneDev &sc, c
         if (tri == 0xFFFFFFFFu) break;  // escaped: no environment emitter
         const uint32_t key = rngKey(pix, g.seed);
         f3 rd = xyz(rd4);
-#if PG_SD_PREFETCH
-        // the guided lookup's jump-grid cell and leaf record, fetched from the ray's o + t d while the triangle and
-        // material gathers resolve; used only when the exact (barycentric) position lands in the same cell
-        uint32_t jCell = 0xFFFFFFFFu, jSpec = 0;
-        uint4 metaSpec = make_uint4(0, 0, 0, 0);
-        if (CAN_GUIDE && g.guiding && sd.built) {
-            const float4 ro = ldS(&p.ray_o[slot]);
-            const SDView sv0 = sdv(sd);
-            jCell = sdJumpCell(sv0, mk(ro.x + hv.x * rd.x, ro.y + hv.x * rd.y, ro.z + hv.x * rd.z));
-            jSpec = sd.jump[jCell];
-        }
-#endif
         Hit h;
         fetchHit(sc, tri, hv.z, hv.w, rd, h);
-#if PG_SD_PREFETCH
-        // the leaf's record behind the triangle loads (index 0, a valid record, where the cell holds a node)
-        if (CAN_GUIDE && g.guiding && sd.built) metaSpec = sd.meta[(jSpec & 0x80000000u) ? (jSpec & 0x7FFFFFFFu) : 0u];
-#endif
         WSET(0, depth);
         WSET(1, __float_as_uint(sc.tshade[(size_t)PG_TRI_SHADE_STRIDE * tri + 2].w));
         WSET3(2, h.p);
@@ -716,19 +501,7 @@ __device__ __forceinline__ void shadeOne(const GParams &g, const SceneDev &sc, c
         // the registers it always did (k_shade_all spills 4 VGPRs); next to the extension-ray stores it spilled 49
         float rrNext = 0.0f;
         if (cull && depth >= (uint32_t)g.rr_depth) rrNext = rng1(key, sample, dimOf(depth, SLOT_RR));
-#if PG_MAT_UNIFORM
-        // one uniform (scalar-cache) load per distinct material of the wave instead of eight 16-B gathers per lane
-        GMat M;
-        for (;;) {
-            const uint32_t u = __builtin_amdgcn_readfirstlane(h.mat);
-            if (h.mat == u) {
-                M = mats[u];
-                break;
-            }
-        }
-#else
         GMat M = mats[h.mat];
-#endif
         if constexpr (TEX) {
             const uint32_t ti = sc.mtex[h.mat];
             if (ti != 0xFFFFFFFFu) {
@@ -756,14 +529,7 @@ __device__ __forceinline__ void shadeOne(const GParams &g, const SceneDev &sc, c
         const bool guide = CAN_GUIDE && g.guiding && sd.built && (M.type & ESmooth) && !(M.type & EDelta) && gRate < 1.0f;
         const SDView sv = sdv(sd);
         uint4 meta = make_uint4(0, 0, 0, 0);
-#if PG_SD_PREFETCH
-        if (guide) {
-            if ((jSpec & 0x80000000u) && sdJumpCell(sv, h.p) == jCell) meta = metaSpec;  // the same leaf
-            else meta = sd.meta[sdLookup(sv, h.p)];
-        }
-#else
         if (guide) meta = sd.meta[sdLookup(sv, h.p)];
-#endif
         // one-sample-MIS BSDF fraction of this vertex (pg_config.bsdf_fraction_bound; oracle guideFraction):
         // PG_FRACTION_LEARNED reads the leaf's learned fraction (meta.z; 0 = not learned yet)
         const float leafAlpha = __uint_as_float(meta.z);
@@ -1802,9 +1568,8 @@ static inline uint32_t blocks(uint64_t n, uint32_t b) { return (uint32_t)((n + b
 
 size_t pg_stack_overflow_words(uint64_t max_threads) {
     if (max_threads == 0) max_threads = (uint64_t)TRACE_MAX_BLOCKS * TRACE_BLOCK;
-    const size_t words = std::max<size_t>(std::max(STACK_DEPTH, PG_BVH4 ? PG_QSTACK_DEPTH : 0) - LDS_STACK,
-                                          2 * (STACK_DEPTH - WIDE_LDS_STACK)) +
-                         (PG_TRACE_PAIR ? kPairRing : 0);  // the paired walks' second band
+    const size_t words = std::max<size_t>(std::max(STACK_DEPTH, PG_QSTACK_DEPTH) - LDS_STACK,
+                                          2 * (STACK_DEPTH - WIDE_LDS_STACK));
     return words * max_threads;
 }
 // threads k_trace_rays launches for n rays: its overflow stride is gridDim.x * TRACE_BLOCK
@@ -1932,7 +1697,7 @@ void pg_launch_rays(hipStream_t s, const GParams &g, const SceneDev &sc, const P
     // the probe queue's shards are bounded as the shadow queue's (both hold vertices of the bounce just shaded)
     const uint32_t pb = (g.doom_probe && !sc.env) ? sb : 0;
     const uint32_t tb =
-        max_shard ? shardGrid(max_shard, (PG_TRACE_PAIR ? 2 : 1) * TRACE_BLOCK, TRACE_MAX_BLOCKS / PG_QSHARDS).x : 0;
+        max_shard ? shardGrid(max_shard, TRACE_BLOCK, TRACE_MAX_BLOCKS / PG_QSHARDS).x : 0;
     if (sb + tb == 0) return;
     if (tb == 0) {  // no trace rows: k_rays needs at least one trace block per shard to stay sharded
         if (count) hipLaunchKernelGGL(k_shadow<true>, dim3(sb), dim3(TRACE_BLOCK), 0, s, sc, p, shq);

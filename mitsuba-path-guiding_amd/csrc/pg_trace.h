@@ -12,7 +12,7 @@ using namespace pgd;
 #endif
 #define STACK_DEPTH 48  // total traversal stack entries (the BVH builder bounds the depth below this)
 #ifndef LDS_STACK
-#define LDS_STACK 16    // binary BVH: top entries in LDS (4 B each: 16 KiB per block), deeper ones spill
+#define LDS_STACK 16    // 4-wide BVH: top entries in LDS (4 B each: 16 KiB per block), deeper ones spill
 #endif
 #ifndef WIDE_LDS_STACK
 #define WIDE_LDS_STACK 8  // wide BVH: top group entries in LDS (8 B each: 16 KiB per block)
@@ -30,36 +30,10 @@ namespace {
 // Path-state accesses (every SoA record is read once and written once per bounce).  Non-temporal
 // loads/stores here measured +1 % on C3 but made results timing-dependent with three lanes in flight
 // (2 outcomes in 12 runs of tools/det_kitchen.py, 1 in 20 without), so they are plain.
-// PG_NT_STATE=1 (A/B builds): the non-temporal variant again (round 5, VERDICT r04 item 2: keep the streamed
-// state out of the XCD's L2 so the BVH and TriAccel working set stays).
-#ifndef PG_NT_STATE
-#define PG_NT_STATE 0
-#endif
-#if PG_NT_STATE
-typedef float pgF4v __attribute__((ext_vector_type(4)));
-typedef unsigned int pgU4v __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 ldS(const float4 *p) {
-    const pgF4v v = __builtin_nontemporal_load(reinterpret_cast<const pgF4v *>(p));
-    return make_float4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ uint4 ldS(const uint4 *p) {
-    const pgU4v v = __builtin_nontemporal_load(reinterpret_cast<const pgU4v *>(p));
-    return make_uint4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ void stS(float4 *p, float4 a) {
-    const pgF4v v = {a.x, a.y, a.z, a.w};
-    __builtin_nontemporal_store(v, reinterpret_cast<pgF4v *>(p));
-}
-__device__ __forceinline__ void stS(uint4 *p, uint4 a) {
-    const pgU4v v = {a.x, a.y, a.z, a.w};
-    __builtin_nontemporal_store(v, reinterpret_cast<pgU4v *>(p));
-}
-#else
 __device__ __forceinline__ float4 ldS(const float4 *p) { return *p; }
 __device__ __forceinline__ uint4 ldS(const uint4 *p) { return *p; }
 __device__ __forceinline__ void stS(float4 *p, float4 a) { *p = a; }
 __device__ __forceinline__ void stS(uint4 *p, uint4 a) { *p = a; }
-#endif
 
 // Traversal statistics (debug build PG_TRAV_STATS=1, make travstats; tools/r06_trav_stats.py): per walk kind
 // (0 closest, 1 any hit) the walks, node visits, triangle tests and executed node-test iterations of whole waves
@@ -74,9 +48,8 @@ __device__ unsigned long long pgTravStats[8];
 // ---------------------------------------------------------------------------------------------
 // BVH traversal.  Replaces ShapeKDTree::rayIntersect / rayIntersectHavran (skdtree.cpp:112-142,
 // sahkdtree3.h:178-308) with the same contract: closest t in [tmin, tmax] (any hit for shadow
-// rays).  Closest-hit rays walk the 4-wide BVH (128-B nodes; the binary BVH's 64-B nodes in PG_BVH4 = 0
-// builds), shadow rays the 8-wide BVH with quantised boxes (80-B nodes); all test the 48-B triangle records
-// of pg_layout.h PG_TRIACCEL (the reference's TriAccel).
+// rays).  Closest-hit rays walk the 4-wide BVH (64-B nodes), shadow rays the 8-wide BVH (80-B nodes), both with
+// quantised boxes; all test the 48-B triangle records of pg_layout.h "Triangle records" (the reference's TriAccel).
 // Stacks: entries [0, LDS) in LDS (columns per thread, stride TRACE_BLOCK: conflict-free), deeper
 // entries in a per-thread column of a global overflow ring (stride = launched threads).
 struct TStack {
@@ -112,24 +85,15 @@ struct WStack {
     }
 };
 
-// Triangle test of every walk (pg_layout.h PG_TRIACCEL): a hit at t in [tmin, tmax] with (bu, bv) the
+// Triangle test of every walk (pg_layout.h "Triangle records"): a hit at t in [tmin, tmax] with (bu, bv) the
 // barycentric weights of p1 and p2.  TriAccel::rayIntersect (triaccel.h:96-157) with the reference's
-// expression order and no contraction: the oracle's t, u, v bit for bit.
-// PG_TRI_PRELOAD=1: the record's three rows loaded together up front instead of rows 1 and 2 only for the
-// lanes whose earlier tests pass (the later rows are cache hits of the same lines): k_rays 23.72-23.83
-// against 23.82-23.91 ms per calibration pass, C3 609-613 against 613-621 Mpaths/s (profiles/r05af_tri_preload/);
-// off by default
-#ifndef PG_TRI_PRELOAD
-#define PG_TRI_PRELOAD 0
-#endif
-// triHitRow0: the test with the record's first row already loaded (the paired walk issues both rays' rows first)
+// expression order and no contraction: the oracle's t, u, v bit for bit.  Rows 1 and 2 are loaded only for the
+// lanes whose earlier tests pass.
+// triHitRow0: the test with the record's first row already loaded (the leaf loops load two triangles' first rows
+// before either test)
 __device__ __forceinline__ bool triHitRow0(const float4 r0, const float4 *__restrict__ tris, uint32_t tr, f3 o, f3 d,
                                            float tmin, float tmax, float &tt, float &bu, float &bv) {
 #pragma clang fp contract(off)
-#if PG_TRI_PRELOAD
-    const float4 r1 = tris[PG_TRI_ROW(tr, 1)];
-    const float2 r2 = *reinterpret_cast<const float2 *>(tris + PG_TRI_ROW(tr, 2));
-#endif
     const uint32_t k = __float_as_uint(r0.w);  // projection axis; (u, v) = the next two axes cyclically
     const float ou = k == 0 ? o.y : (k == 1 ? o.z : o.x), ov = k == 0 ? o.z : (k == 1 ? o.x : o.y);
     const float ok = k == 0 ? o.x : (k == 1 ? o.y : o.z);
@@ -137,15 +101,11 @@ __device__ __forceinline__ bool triHitRow0(const float4 r0, const float4 *__rest
     const float dk = k == 0 ? d.x : (k == 1 ? d.y : d.z);
     tt = (r0.z - ou * r0.x - ov * r0.y - ok) / (du * r0.x + dv * r0.y + dk);
     if (!(tt >= tmin && tt <= tmax)) return false;
-#if !PG_TRI_PRELOAD
     const float4 r1 = tris[PG_TRI_ROW(tr, 1)];
-#endif
     const float hu = ou + tt * du - r1.x, hv = ov + tt * dv - r1.y;
     const float u = hv * r1.z + hu * r1.w;
     if (!(u >= 0.0f)) return false;
-#if !PG_TRI_PRELOAD
     const float2 r2 = *reinterpret_cast<const float2 *>(tris + PG_TRI_ROW(tr, 2));
-#endif
     const float v = hu * r2.x + hv * r2.y;
     if (!(v >= 0.0f && u + v <= 1.0f)) return false;
     bu = u;
@@ -154,24 +114,7 @@ __device__ __forceinline__ bool triHitRow0(const float4 r0, const float4 *__rest
 }
 __device__ __forceinline__ bool triHit(const float4 *__restrict__ tris, uint32_t tr, f3 o, f3 d, float tmin, float tmax,
                                        float &tt, float &bu, float &bv) {
-#if PG_TRIACCEL
     return triHitRow0(tris[PG_TRI_ROW(tr, 0)], tris, tr, o, d, tmin, tmax, tt, bu, bv);
-#else
-    const float4 w0 = tris[PG_TRI_ROW(tr, 0)];
-    float dz = d.x * w0.x + d.y * w0.y + d.z * w0.z;
-    float oz = w0.w - (o.x * w0.x + o.y * w0.y + o.z * w0.z);
-    tt = oz / dz;
-    if (!(tt >= tmin && tt <= tmax)) return false;
-    const float4 w1 = tris[PG_TRI_ROW(tr, 1)];
-    float a = (w1.w + o.x * w1.x + o.y * w1.y + o.z * w1.z) + tt * (d.x * w1.x + d.y * w1.y + d.z * w1.z);
-    if (!(a >= 0.0f && a <= 1.0f)) return false;
-    const float4 w2 = tris[PG_TRI_ROW(tr, 2)];
-    float b = (w2.w + o.x * w2.x + o.y * w2.y + o.z * w2.z) + tt * (d.x * w2.x + d.y * w2.y + d.z * w2.z);
-    if (!(b >= 0.0f && a + b <= 1.0f)) return false;
-    bu = b;             // weight of p1
-    bv = 1.0f - a - b;  // weight of p2
-    return true;
-#endif
 }
 
 // Closest-hit accept rule of every walk: a smaller t, or an equal t (shared edges, coplanar triangles)
@@ -181,11 +124,7 @@ __device__ __forceinline__ bool triHit(const float4 *__restrict__ tris, uint32_t
 __device__ __forceinline__ bool acceptHit(const float4 *__restrict__ tris, float tt, float tmax, uint32_t tr,
                                           uint32_t hitTri) {
     if (tt < tmax || hitTri == 0xFFFFFFFFu) return true;
-#if PG_TRIACCEL
     return __float_as_uint(tris[PG_TRI_ROW(tr, 2)].z) < __float_as_uint(tris[PG_TRI_ROW(hitTri, 2)].z);
-#else
-    return tr < hitTri;  // Woop rows carry no original id: BVH order (A/B builds only)
-#endif
 }
 
 __device__ __forceinline__ float qbyte(uint32_t lo, uint32_t hi, int s) {
@@ -209,25 +148,12 @@ __device__ __forceinline__ uint32_t permuteXor8(uint32_t m, uint32_t x) {
     return m;
 }
 
-// PG_NODE_PK (round 6, A/B, off by default): a slot's near- and far-plane distances of one axis as one packed fma
-// (v_pk_fma_f32 computes two fp32 lanes per instruction at the VALU's full rate), the same fmas bit for bit
-#ifndef PG_NODE_PK
-#define PG_NODE_PK 0
-#endif
-typedef float pgf2 __attribute__((ext_vector_type(2)));
-
-// PG_LEAF_PAIRS (default): leaf triangles are taken two at a time with both first rows loaded before either
-// test (the tests, and so the accepted hit, stay in triangle order): closest hits k_rays 22.1 against 22.5 ms
-// per calibration pass, C3 634-635 against 625-626 Mpaths/s (profiles/r06_leafpairs/).  PG_LEAF_PAIRS=3 / 4 take
-// three / four per step: k_rays 22.13 / 22.42 against 22.02 ms (profiles/r06_leafgroup/)
-#ifndef PG_LEAF_PAIRS
-#define PG_LEAF_PAIRS 1
-#endif
-// the same for the 8-wide walk's triangle groups (shadow rays): k_rays 21.75 against 22.21 ms, C3 653 against
-// 649 Mpaths/s (profiles/r06_wideleafpairs/)
-#ifndef PG_WIDE_LEAF_PAIRS
-#define PG_WIDE_LEAF_PAIRS 1
-#endif
+// Leaf triangles are taken two at a time with both first rows loaded before either test (the tests, and so the
+// accepted hit, stay in triangle order): closest hits (leafTest) k_rays 22.1 against 22.5 ms per calibration pass,
+// C3 634-635 against 625-626 Mpaths/s (profiles/r06_leafpairs/); three / four per step: k_rays 22.13 / 22.42 against
+// 22.02 ms (profiles/r06_leafgroup/).  The same for the 8-wide walk's triangle groups (shadow rays): k_rays 21.75
+// against 22.21 ms, C3 653 against 649 Mpaths/s (profiles/r06_wideleafpairs/); the statistics build counts its
+// triangle tests in the one-at-a-time loop.
 // Traversal of the 8-wide BVH (after Ylitie, Karras & Laine 2017): the current node group
 // G = (child_base, hit bits 24..31 in octant order | imask bits 0..7) and triangle group
 // T = (tri_base, hit bits 0..23); one node is opened per step, its remaining siblings stay on the
@@ -285,19 +211,11 @@ __device__ __forceinline__ bool traverseWide(const float4 *__restrict__ nodes, c
             uint32_t hitSlots = 0;
 #pragma unroll
             for (int s = 0; s < 8; ++s) {
-#if PG_NODE_PK  // (near, far) of an axis as one packed fma (pg_trace.h traverse4)
-                const pgf2 tx = __builtin_elementwise_fma(pgf2{qbyte(nX0, nX1, s), qbyte(fX0, fX1, s)}, pgf2{ax, ax}, pgf2{bx, bx});
-                const pgf2 ty = __builtin_elementwise_fma(pgf2{qbyte(nY0, nY1, s), qbyte(fY0, fY1, s)}, pgf2{ay, ay}, pgf2{by, by});
-                const pgf2 tz = __builtin_elementwise_fma(pgf2{qbyte(nZ0, nZ1, s), qbyte(fZ0, fZ1, s)}, pgf2{az, az}, pgf2{bz, bz});
-                const float cmin = max3f(tx.x, ty.x, fmaxf(tz.x, tmin));
-                const float cmax = min3f(tx.y, ty.y, fminf(tz.y, tmax));
-#else
                 const float tnx = fmaf(qbyte(nX0, nX1, s), ax, bx), tfx = fmaf(qbyte(fX0, fX1, s), ax, bx);
                 const float tny = fmaf(qbyte(nY0, nY1, s), ay, by), tfy = fmaf(qbyte(fY0, fY1, s), ay, by);
                 const float tnz = fmaf(qbyte(nZ0, nZ1, s), az, bz), tfz = fmaf(qbyte(fZ0, fZ1, s), az, bz);
                 const float cmin = max3f(tnx, tny, fmaxf(tnz, tmin));
                 const float cmax = min3f(tfx, tfy, fminf(tfz, tmax));
-#endif
                 hitSlots |= (cmin <= cmax ? 1u : 0u) << s;
             }
             const uint32_t nodeHits = permuteXor8(hitSlots & imask, octinv) << 24;
@@ -311,7 +229,7 @@ __device__ __forceinline__ bool traverseWide(const float4 *__restrict__ nodes, c
             G = make_uint2(__float_as_uint(n1.x), nodeHits | imask);
             T = make_uint2(__float_as_uint(n1.y), triHits);
         }
-#if PG_WIDE_LEAF_PAIRS && PG_TRIACCEL && !PG_TRAV_STATS
+#if !PG_TRAV_STATS
         while (T.y != 0) {  // two triangles per step, both first rows loaded up front
             const uint32_t ta = T.x + (uint32_t)(__ffs(T.y) - 1);
             T.y &= T.y - 1u;
@@ -372,15 +290,14 @@ __device__ __forceinline__ bool traverseWide(const float4 *__restrict__ nodes, c
     return found;
 }
 
-// Postponed-leaf triangle tests shared by the binary and the 4-wide closest-hit walks: every
+// Postponed-leaf triangle tests of the 4-wide closest-hit walk: every
 // triangle of leaf ref `leaf` (< 0: ~leaf = first << 4 | count) against the ray.
 template <bool ANY>
 __device__ __forceinline__ bool leafTest(const float4 *__restrict__ tris, int leaf, f3 o, f3 d, float tmin,
                                          float &tmax, uint32_t &hitTri, float &hu, float &hv, bool &found) {
     const uint32_t lr = ~(uint32_t)leaf;
     const uint32_t first = lr >> 4, cnt = lr & 15u;
-#if PG_LEAF_PAIRS && PG_TRIACCEL
-    constexpr uint32_t G = PG_LEAF_PAIRS > 1 ? PG_LEAF_PAIRS : 2;  // triangles per step
+    constexpr uint32_t G = 2;  // triangles per step
     for (uint32_t k = 0; k < cnt; k += G) {
         float4 r[G];
 #pragma unroll
@@ -399,21 +316,6 @@ __device__ __forceinline__ bool leafTest(const float4 *__restrict__ tris, int le
             }
         }
     }
-#else
-    for (uint32_t k = 0; k < cnt; ++k) {
-        const uint32_t tr = first + k;
-        float tt, bu, bv;
-        // equal distances: the lower original triangle index (acceptHit)
-        if (triHit(tris, tr, o, d, tmin, tmax, tt, bu, bv) && acceptHit(tris, tt, tmax, tr, hitTri)) {
-            found = true;
-            if (ANY) return true;
-            tmax = tt;
-            hitTri = tr;
-            hu = bu;
-            hv = bv;
-        }
-    }
-#endif
     return false;
 }
 
@@ -428,22 +330,19 @@ __device__ __forceinline__ void cxch(float &ka, int &ra, float &kb, int &rb) {
     ra = r;
 }
 
-// Per-ray slab-test setup of the closest-hit walks.  t = fma(plane, idir, add) per axis; with
-// PG_ROBUST_BOX (default) the addends move each axis's near plane earlier and its far plane later by
+// Per-ray slab-test setup of the closest-hit walk.  t = fma(plane, idir, add) per axis;
+// the addends move each axis's near plane earlier and its far plane later by
 // 2^-21 |o_a idir_a| -- a spatial padding of 2^-21 |o_a| along that axis, which bounds the rounding of
 // o * idir and of the fma -- and box intervals are compared as cmin <= cmax (1 + 2^-21) for the
 // rounding relative to t.  Without it a ray clipping a box edge far from the origin could see its
 // rounded interval come out empty while it hits the triangle inside (tests/test_bvh4_build.py, a
 // strip of triangles spanning 1 to 1.6e5: 0.55 % of the rays).  It costs one multiply per box; a
 // global slack of 1e-6 max|o idir| instead made the kitchen's traversal 2.8x slower (near-axis rays).
-#ifndef PG_ROBUST_BOX
-#define PG_ROBUST_BOX 1
-#endif
 struct SlabRay {
     f3 idir, addLo, addHi;
     float tslack;  // culling-distance slack (tie rule): a few ulps of the largest |o_a idir_a|
 };
-constexpr float kBoxRel = PG_ROBUST_BOX ? 1.000000477f : 1.0f;  // 1 + 2^-21
+constexpr float kBoxRel = 1.000000477f;  // 1 + 2^-21
 __device__ __forceinline__ SlabRay slabRay(f3 o, f3 d) {
     const float eps = 1e-30f;
     SlabRay r;
@@ -451,7 +350,7 @@ __device__ __forceinline__ SlabRay slabRay(f3 o, f3 d) {
                 1.0f / (fabsf(d.z) > eps ? d.z : copysignf(eps, d.z)));
     const f3 ood = o * r.idir;
     r.tslack = 1e-6f * fmaxf(fmaxf(fabsf(ood.x), fabsf(ood.y)), fabsf(ood.z));
-    const float k = PG_ROBUST_BOX ? 4.76837158e-7f : 0.0f;  // 2^-21
+    const float k = 4.76837158e-7f;  // 2^-21
     const f3 se = mk(copysignf(k * fabsf(ood.x), r.idir.x), copysignf(k * fabsf(ood.y), r.idir.y),
                      copysignf(k * fabsf(ood.z), r.idir.z));
     r.addLo = -ood - se;  // the lo plane is the near one for idir >= 0
@@ -459,34 +358,34 @@ __device__ __forceinline__ SlabRay slabRay(f3 o, f3 d) {
     return r;
 }
 
-// Closest-hit walk of the 4-wide BVH (PG_BVH4): one 128-B node per visit instead of two 64-B binary
-// nodes, its hit children visited nearest first (a 5-exchange sorting network on the entry
-// distances; the others pushed far to near), with the binary walk's while-while loop, postponed
-// leaves, tie rule and widened culling distance, so it returns the same hit.
-// LTOP: nodes [0, ntop) are read from `lnodes` (the breadth-first top levels, staged in LDS by the caller)
-// PG_NODE_NEARFAR (round 6, default): each axis's near and far planes chosen once per node by the ray's
+// Closest-hit walk of the 4-wide BVH: one 64-B node per visit, its hit children visited nearest first (a
+// 5-exchange sorting network on the entry distances; the others pushed far to near).
+// While-while traversal with postponed leaves (Aila & Laine 2009): lanes keep descending inner
+// nodes until every lane of the wave holds a leaf, then all lanes test triangles together.  This
+// keeps the 64-wide wave in one code path most of the time (if-if traversal measured 23 % lane
+// utilisation on gfx950).
+// Boxes are culled against tmax widened by the slab-distance rounding (tcull): a triangle that ties
+// with the current hit (shared edge, coplanar) can sit in a box whose rounded entry distance
+// lands just past tmax, and skipping it would make the tie-break (lower index, acceptHit) depend on
+// traversal order, i.e. on which paths share the wave (box intervals: slabRay).
+// Each axis's near and far planes are chosen once per node by the ray's
 // direction sign (the lo plane is the near one for idir >= 0), so a slot's entry and exit distances are one
 // max3 / min3 each instead of a min and a max per axis.  The same distances and comparisons as the min/max
 // form bit for bit: for a non-empty slot lo <= hi and the padded addends keep their order, so min(lo-plane t,
 // hi-plane t) IS the near plane's t (empty slots are rejected by their ref either way).  The walk is VALU-bound
 // (~4 cycles x 1.0 M VALU wave-instructions per SIMD per k_rays launch against its ~4.8 M cycles)
-#ifndef PG_NODE_NEARFAR
-#define PG_NODE_NEARFAR 1
-#endif
-template <bool ANY, bool LTOP = false>
+template <bool ANY>
 __device__ __forceinline__ bool traverse4(const float4 *__restrict__ nodes, const float4 *__restrict__ tris, f3 o, f3 d,
                                           float tmin, float &tmax, uint32_t &hitTri, float &hu, float &hv,
-                                          const TStack &stk, const float4 *lnodes = nullptr, int ntop = 0) {
+                                          const TStack &stk) {
     const int DONE = 0x7fffffff;
     const float INF = __builtin_huge_valf();
     const SlabRay sr = slabRay(o, d);
     const f3 idir = sr.idir, aLo = sr.addLo, aHi = sr.addHi;
     const float tslack = sr.tslack;
-#if PG_QNODE_QUANT && PG_NODE_NEARFAR
     const bool negx = idir.x < 0.0f, negy = idir.y < 0.0f, negz = idir.z < 0.0f;
     const f3 aN = mk(negx ? aHi.x : aLo.x, negy ? aHi.y : aLo.y, negz ? aHi.z : aLo.z);
     const f3 aF = mk(negx ? aLo.x : aHi.x, negy ? aLo.y : aHi.y, negz ? aLo.z : aHi.z);
-#endif
     int sp = 0;
     int node = 0;
     int leaf = 0;
@@ -503,57 +402,23 @@ __device__ __forceinline__ bool traverse4(const float4 *__restrict__ nodes, cons
             const float4 *np = nodes + (size_t)PG_QNODE_F4 * node;
             float k[4];
             int r[4];
-#if PG_QNODE_QUANT
             // planes origin + q 2^e: t = q (2^e idir) + (origin - o) idir, the latter padded outward by
             // slabRay's addends and by 2^-22 |origin idir| (its own rounding)
-            float4 n0, rf, q0, q1;
-            if (LTOP && node < ntop) {  // LDS loads for the staged top levels, global loads below them
-                const float4 *lp = lnodes + (size_t)PG_QNODE_F4 * node;
-                n0 = lp[0];
-                rf = lp[1];
-                q0 = lp[2];
-                q1 = lp[3];
-            } else {
-                n0 = np[0];
-                rf = np[1];
-                q0 = np[2];
-                q1 = np[3];
-            }
+            const float4 n0 = np[0], rf = np[1], q0 = np[2], q1 = np[3];
             const uint32_t e = __float_as_uint(n0.w);
             const float sx = __uint_as_float((e & 0xFFu) << 23) * idir.x;
             const float sy = __uint_as_float(((e >> 8) & 0xFFu) << 23) * idir.y;
             const float sz = __uint_as_float(((e >> 16) & 0xFFu) << 23) * idir.z;
-#if PG_NODE_NEARFAR
-            // |padding| per axis; near addend - it, far addend + it (the sign-carrying form below, unrolled)
+            // |padding| per axis; near addend - it, far addend + it
             const float ax = 2.38418579e-7f * fabsf(n0.x * idir.x);
             const float ay = 2.38418579e-7f * fabsf(n0.y * idir.y);
             const float az = 2.38418579e-7f * fabsf(n0.z * idir.z);
-#if !PG_NODE_PK
             const float bnx = fmaf(n0.x, idir.x, aN.x) - ax, bfx = fmaf(n0.x, idir.x, aF.x) + ax;
             const float bny = fmaf(n0.y, idir.y, aN.y) - ay, bfy = fmaf(n0.y, idir.y, aF.y) + ay;
             const float bnz = fmaf(n0.z, idir.z, aN.z) - az, bfz = fmaf(n0.z, idir.z, aF.z) + az;
-#endif
             const uint32_t wnx = __float_as_uint(negx ? q0.y : q0.x), wfx = __float_as_uint(negx ? q0.x : q0.y);
             const uint32_t wny = __float_as_uint(negy ? q0.w : q0.z), wfy = __float_as_uint(negy ? q0.z : q0.w);
             const uint32_t wnz = __float_as_uint(negz ? q1.y : q1.x), wfz = __float_as_uint(negz ? q1.x : q1.y);
-#if PG_NODE_PK
-            // (near, far) of an axis as one packed fma (v_pk_fma_f32: two lanes of fp32 per instruction)
-            const pgf2 sx2 = {sx, sx}, sy2 = {sy, sy}, sz2 = {sz, sz};
-            const pgf2 bx2 = __builtin_elementwise_fma(pgf2{n0.x, n0.x}, pgf2{idir.x, idir.x}, pgf2{aN.x, aF.x}) + pgf2{-ax, ax};
-            const pgf2 by2 = __builtin_elementwise_fma(pgf2{n0.y, n0.y}, pgf2{idir.y, idir.y}, pgf2{aN.y, aF.y}) + pgf2{-ay, ay};
-            const pgf2 bz2 = __builtin_elementwise_fma(pgf2{n0.z, n0.z}, pgf2{idir.z, idir.z}, pgf2{aN.z, aF.z}) + pgf2{-az, az};
-#define PG_QB(w, i) ((float)(((w) >> (8 * (i))) & 0xFFu))
-#define PG_Q4_SLOT(i, c)                                                                              \
-    {                                                                                                 \
-        const pgf2 tx = __builtin_elementwise_fma(pgf2{PG_QB(wnx, i), PG_QB(wfx, i)}, sx2, bx2);        \
-        const pgf2 ty = __builtin_elementwise_fma(pgf2{PG_QB(wny, i), PG_QB(wfy, i)}, sy2, by2);        \
-        const pgf2 tz = __builtin_elementwise_fma(pgf2{PG_QB(wnz, i), PG_QB(wfz, i)}, sz2, bz2);        \
-        const float cmin = fmaxf(fmaxf(tx.x, ty.x), fmaxf(tz.x, tmin));                               \
-        const float cmax = fminf(fminf(tx.y, ty.y), fminf(tz.y, tcull));                              \
-        r[i] = __float_as_int(rf.c);                                                                  \
-        k[i] = (cmin <= cmax * kBoxRel && r[i] != PG_QNODE_EMPTY) ? cmin : INF;                       \
-    }
-#else
 #define PG_QB(w, i) ((float)(((w) >> (8 * (i))) & 0xFFu))
 #define PG_Q4_SLOT(i, c)                                                                              \
     {                                                                                                 \
@@ -565,43 +430,6 @@ __device__ __forceinline__ bool traverse4(const float4 *__restrict__ nodes, cons
         r[i] = __float_as_int(rf.c);                                                                  \
         k[i] = (cmin <= cmax * kBoxRel && r[i] != PG_QNODE_EMPTY) ? cmin : INF;                       \
     }
-#endif
-#else
-            const float px = copysignf(2.38418579e-7f * fabsf(n0.x * idir.x), idir.x);
-            const float py = copysignf(2.38418579e-7f * fabsf(n0.y * idir.y), idir.y);
-            const float pz = copysignf(2.38418579e-7f * fabsf(n0.z * idir.z), idir.z);
-            const float bxl = fmaf(n0.x, idir.x, aLo.x) - px, bxh = fmaf(n0.x, idir.x, aHi.x) + px;
-            const float byl = fmaf(n0.y, idir.y, aLo.y) - py, byh = fmaf(n0.y, idir.y, aHi.y) + py;
-            const float bzl = fmaf(n0.z, idir.z, aLo.z) - pz, bzh = fmaf(n0.z, idir.z, aHi.z) + pz;
-            const uint32_t wlx = __float_as_uint(q0.x), whx = __float_as_uint(q0.y), wly = __float_as_uint(q0.z),
-                           why = __float_as_uint(q0.w), wlz = __float_as_uint(q1.x), whz = __float_as_uint(q1.y);
-#define PG_QB(w, i) ((float)(((w) >> (8 * (i))) & 0xFFu))
-#define PG_Q4_SLOT(i, c)                                                                              \
-    {                                                                                                 \
-        const float x0 = fmaf(PG_QB(wlx, i), sx, bxl), x1 = fmaf(PG_QB(whx, i), sx, bxh);              \
-        const float y0 = fmaf(PG_QB(wly, i), sy, byl), y1 = fmaf(PG_QB(why, i), sy, byh);              \
-        const float z0 = fmaf(PG_QB(wlz, i), sz, bzl), z1 = fmaf(PG_QB(whz, i), sz, bzh);              \
-        const float cmin = fmaxf(fmaxf(fminf(x0, x1), fminf(y0, y1)), fmaxf(fminf(z0, z1), tmin));    \
-        const float cmax = fminf(fminf(fmaxf(x0, x1), fmaxf(y0, y1)), fminf(fmaxf(z0, z1), tcull));   \
-        r[i] = __float_as_int(rf.c);                                                                  \
-        k[i] = (cmin <= cmax * kBoxRel && r[i] != PG_QNODE_EMPTY) ? cmin : INF;                       \
-    }
-#endif
-#else
-            const float4 *fp = (LTOP && node < ntop) ? lnodes + (size_t)PG_QNODE_F4 * node : np;
-            const float4 lx = fp[0], hx = fp[1], ly = fp[2], hy = fp[3], lz = fp[4], hz = fp[5];
-            const float4 rf = fp[6];
-#define PG_Q4_SLOT(i, c)                                                                              \
-    {                                                                                                 \
-        const float x0 = fmaf(lx.c, idir.x, aLo.x), x1 = fmaf(hx.c, idir.x, aHi.x);                   \
-        const float y0 = fmaf(ly.c, idir.y, aLo.y), y1 = fmaf(hy.c, idir.y, aHi.y);                   \
-        const float z0 = fmaf(lz.c, idir.z, aLo.z), z1 = fmaf(hz.c, idir.z, aHi.z);                   \
-        const float cmin = fmaxf(fmaxf(fminf(x0, x1), fminf(y0, y1)), fmaxf(fminf(z0, z1), tmin));    \
-        const float cmax = fminf(fminf(fmaxf(x0, x1), fmaxf(y0, y1)), fminf(fmaxf(z0, z1), tcull));   \
-        r[i] = __float_as_int(rf.c);                                                                  \
-        k[i] = (cmin <= cmax * kBoxRel && r[i] != PG_QNODE_EMPTY) ? cmin : INF;                       \
-    }
-#endif
             PG_Q4_SLOT(0, x) PG_Q4_SLOT(1, y) PG_Q4_SLOT(2, z) PG_Q4_SLOT(3, w)
 #undef PG_Q4_SLOT
 #undef PG_QB
@@ -641,304 +469,21 @@ __device__ __forceinline__ bool traverse4(const float4 *__restrict__ nodes, cons
     return found;
 }
 
-// ---- the 4-wide closest-hit walk as a resumable state (PG_TRACE_PERSIST, pg_kernels.hip traceRowsPersist) ----
-// The same per-ray constants, node test, sorting network, postponed leaf, tie rule and culling distance as
-// traverse4's default configuration (PG_QNODE_QUANT, PG_NODE_NEARFAR), split so a lane can run one round of
-// the while-while loop at a time: between rounds, lanes whose ray finished take a new ray, so the wave's lanes
-// stay busy instead of waiting for the round's longest ray.  Each ray's own sequence of node visits and leaf
-// tests is traverse4's, so it returns the same hit.
-struct Walk4 {
-    f3 o, d, idir, aN, aF;
-    float tmin, tmax, tslack, hu, hv;
-    uint32_t hitTri;
-    int node, leaf, sp;
-    bool negx, negy, negz;
-};
-__device__ __forceinline__ void walk4Start(Walk4 &w, f3 o, f3 d, float tmin, float tmax) {
-    const SlabRay sr = slabRay(o, d);
-    w.o = o;
-    w.d = d;
-    w.idir = sr.idir;
-    w.tslack = sr.tslack;
-    w.negx = sr.idir.x < 0.0f;
-    w.negy = sr.idir.y < 0.0f;
-    w.negz = sr.idir.z < 0.0f;
-    w.aN = mk(w.negx ? sr.addHi.x : sr.addLo.x, w.negy ? sr.addHi.y : sr.addLo.y, w.negz ? sr.addHi.z : sr.addLo.z);
-    w.aF = mk(w.negx ? sr.addLo.x : sr.addHi.x, w.negy ? sr.addLo.y : sr.addHi.y, w.negz ? sr.addLo.z : sr.addHi.z);
-    w.tmin = tmin;
-    w.tmax = tmax;
-    w.hitTri = 0xFFFFFFFFu;
-    w.hu = w.hv = 0.0f;
-    w.node = 0;
-    w.leaf = 0;
-    w.sp = 0;
-}
-// one node of the 4-wide BVH (quantised: origin + exponents, child refs, near/far byte planes)
-struct QNode4 {
-    float4 n0, rf, q0, q1;
-};
-__device__ __forceinline__ QNode4 walk4Fetch(const float4 *__restrict__ nodes, int node) {
-    const float4 *np = nodes + (size_t)PG_QNODE_F4 * node;
-    return QNode4{np[0], np[1], np[2], np[3]};
-}
-// one node visit of traverse4 on fetched node data: w.node becomes the nearest hit child (the others pushed
-// far to near) or the popped entry, and a leaf is parked in w.leaf when that slot is free
-__device__ __forceinline__ void walk4Visit(Walk4 &w, const QNode4 &nd, float tcull, const TStack &stk) {
-    const int DONE = 0x7fffffff;
-    const float INF = __builtin_huge_valf();
-    const float4 n0 = nd.n0, rf = nd.rf, q0 = nd.q0, q1 = nd.q1;
-    const f3 idir = w.idir;
-    const uint32_t e = __float_as_uint(n0.w);
-    const float sx = __uint_as_float((e & 0xFFu) << 23) * idir.x;
-    const float sy = __uint_as_float(((e >> 8) & 0xFFu) << 23) * idir.y;
-    const float sz = __uint_as_float(((e >> 16) & 0xFFu) << 23) * idir.z;
-    const float ax = 2.38418579e-7f * fabsf(n0.x * idir.x);
-    const float ay = 2.38418579e-7f * fabsf(n0.y * idir.y);
-    const float az = 2.38418579e-7f * fabsf(n0.z * idir.z);
-    const float bnx = fmaf(n0.x, idir.x, w.aN.x) - ax, bfx = fmaf(n0.x, idir.x, w.aF.x) + ax;
-    const float bny = fmaf(n0.y, idir.y, w.aN.y) - ay, bfy = fmaf(n0.y, idir.y, w.aF.y) + ay;
-    const float bnz = fmaf(n0.z, idir.z, w.aN.z) - az, bfz = fmaf(n0.z, idir.z, w.aF.z) + az;
-    const uint32_t wnx = __float_as_uint(w.negx ? q0.y : q0.x), wfx = __float_as_uint(w.negx ? q0.x : q0.y);
-    const uint32_t wny = __float_as_uint(w.negy ? q0.w : q0.z), wfy = __float_as_uint(w.negy ? q0.z : q0.w);
-    const uint32_t wnz = __float_as_uint(w.negz ? q1.y : q1.x), wfz = __float_as_uint(w.negz ? q1.x : q1.y);
-    float k[4];
-    int r[4];
-#define PG_QB(w_, i) ((float)(((w_) >> (8 * (i))) & 0xFFu))
-#define PG_W4_SLOT(i, c)                                                                              \
-    {                                                                                                 \
-        const float tnx = fmaf(PG_QB(wnx, i), sx, bnx), tfx = fmaf(PG_QB(wfx, i), sx, bfx);           \
-        const float tny = fmaf(PG_QB(wny, i), sy, bny), tfy = fmaf(PG_QB(wfy, i), sy, bfy);           \
-        const float tnz = fmaf(PG_QB(wnz, i), sz, bnz), tfz = fmaf(PG_QB(wfz, i), sz, bfz);           \
-        const float cmin = fmaxf(fmaxf(tnx, tny), fmaxf(tnz, w.tmin));                                \
-        const float cmax = fminf(fminf(tfx, tfy), fminf(tfz, tcull));                                 \
-        r[i] = __float_as_int(rf.c);                                                                  \
-        k[i] = (cmin <= cmax * kBoxRel && r[i] != PG_QNODE_EMPTY) ? cmin : INF;                       \
-    }
-    PG_W4_SLOT(0, x) PG_W4_SLOT(1, y) PG_W4_SLOT(2, z) PG_W4_SLOT(3, w)
-#undef PG_W4_SLOT
-#undef PG_QB
-    cxch(k[0], r[0], k[1], r[1]);
-    cxch(k[2], r[2], k[3], r[3]);
-    cxch(k[0], r[0], k[2], r[2]);
-    cxch(k[1], r[1], k[3], r[3]);
-    cxch(k[1], r[1], k[2], r[2]);
-    if (k[0] == INF) {
-        w.node = w.sp > 0 ? (int)stk.get(--w.sp) : DONE;
-    } else {
-        w.node = r[0];
-        if (k[3] != INF && w.sp < PG_QSTACK_DEPTH) stk.put(w.sp++, (uint32_t)r[3]);
-        if (k[2] != INF && w.sp < PG_QSTACK_DEPTH) stk.put(w.sp++, (uint32_t)r[2]);
-        if (k[1] != INF && w.sp < PG_QSTACK_DEPTH) stk.put(w.sp++, (uint32_t)r[1]);
-    }
-    if (w.node < 0 && w.leaf >= 0) {
-        w.leaf = w.node;
-        w.node = w.sp > 0 ? (int)stk.get(--w.sp) : DONE;
-    }
-}
-// after a parked leaf's triangles: the next parked entry (traverse4's leaf loop step)
-__device__ __forceinline__ void walk4NextLeaf(Walk4 &w, const TStack &stk) {
-    const int DONE = 0x7fffffff;
-    w.leaf = w.node;
-    if (w.node < 0) w.node = w.sp > 0 ? (int)stk.get(--w.sp) : DONE;
-}
-// one round of traverse4's outer loop (the inner node loop until every lane of the round holds a leaf, then
-// the postponed leaves); returns true when the walk is over (w.hitTri = ~0: no hit)
-__device__ __forceinline__ bool walk4Round(Walk4 &w, const float4 *__restrict__ nodes, const float4 *__restrict__ tris,
-                                           const TStack &stk) {
-    const int DONE = 0x7fffffff;
-    bool found = false;
-    const float tcull = w.tmax * 1.000001f + w.tslack;
-    while (w.node >= 0 && w.node != DONE) {
-        walk4Visit(w, walk4Fetch(nodes, w.node), tcull, stk);
-        if (!__any(w.leaf >= 0)) break;
-    }
-    while (w.leaf < 0) {
-        leafTest<false>(tris, w.leaf, w.o, w.d, w.tmin, w.tmax, w.hitTri, w.hu, w.hv, found);
-        walk4NextLeaf(w, stk);
-    }
-    return w.node == DONE;
-}
-
-// ---- two closest-hit walks per lane, interleaved (PG_TRACE_PAIR, pg_kernels.hip traceRowsPair) ----
-// Each step issues both rays' node (or triangle) loads before either ray's test, so a lane keeps two
-// dependent chains' requests in flight.  Each walk is traverse4's while-while walk (the inner loop runs
-// while a descending ray of the wave has a free leaf slot; then every parked leaf is tested), so the hits
-// are traverse4's: the closest (t, original index) over the visited boxes, whatever the visit order.
-__device__ __forceinline__ void walk4Idle(Walk4 &w) {
-    w.node = 0x7fffffff;
-    w.leaf = 0;
-    w.sp = 0;
-    w.hitTri = 0xFFFFFFFFu;
-    w.tmax = 0.0f;
-    w.hu = w.hv = 0.0f;
-}
-// one triangle of a parked leaf, its first row already loaded (triHitRow0: triHit's test bit for bit)
-__device__ __forceinline__ void walk4Tri(Walk4 &w, const float4 *__restrict__ tris, uint32_t tr, float4 r0) {
-    float tt, bu, bv;
-    if (triHitRow0(r0, tris, tr, w.o, w.d, w.tmin, w.tmax, tt, bu, bv) && acceptHit(tris, tt, w.tmax, tr, w.hitTri)) {
-        w.tmax = tt;
-        w.hitTri = tr;
-        w.hu = bu;
-        w.hv = bv;
-    }
-}
-__device__ __forceinline__ void walk4Pair(Walk4 &a, Walk4 &b, const float4 *__restrict__ nodes,
-                                          const float4 *__restrict__ tris, const TStack &sa, const TStack &sb) {
-    const int DONE = 0x7fffffff;
-    while (a.node != DONE || b.node != DONE) {
-        const float ca = a.tmax * 1.000001f + a.tslack, cb = b.tmax * 1.000001f + b.tslack;
-        for (;;) {
-            const bool da = a.node >= 0 && a.node != DONE, db = b.node >= 0 && b.node != DONE;
-            if (!(da || db)) break;
-            QNode4 na, nb;
-            if (da) na = walk4Fetch(nodes, a.node);
-            if (db) nb = walk4Fetch(nodes, b.node);
-            if (da) walk4Visit(a, na, ca, sa);
-            if (db) walk4Visit(b, nb, cb, sb);
-            const bool free = (a.leaf >= 0 && a.node >= 0 && a.node != DONE) || (b.leaf >= 0 && b.node >= 0 && b.node != DONE);
-            if (!__any(free)) break;
-        }
-        for (;;) {
-            const bool la = a.leaf < 0, lb = b.leaf < 0;
-            if (!(la || lb)) break;
-            const uint32_t ra = la ? ~(uint32_t)a.leaf : 0u, rb = lb ? ~(uint32_t)b.leaf : 0u;
-            const uint32_t fa = ra >> 4, na = ra & 15u, fb = rb >> 4, nb = rb & 15u;
-            for (uint32_t k = 0; k < na || k < nb; ++k) {
-                float4 ta, tb;
-                if (k < na) ta = tris[PG_TRI_ROW(fa + k, 0)];
-                if (k < nb) tb = tris[PG_TRI_ROW(fb + k, 0)];
-                if (k < na) walk4Tri(a, tris, fa + k, ta);
-                if (k < nb) walk4Tri(b, tris, fb + k, tb);
-            }
-            if (la) walk4NextLeaf(a, sa);
-            if (lb) walk4NextLeaf(b, sb);
-        }
-    }
-}
-
-// While-while traversal with postponed leaves (Aila & Laine 2009): lanes keep descending inner
-// nodes until every lane of the wave holds a leaf, then all lanes test triangles together.  This
-// keeps the 64-wide wave in one code path most of the time (if-if traversal measured 23 % lane
-// utilisation on gfx950).
-// LTOP: nodes [0, ntop) are read from `lnodes` (the top levels, staged in LDS by the caller).
-template <bool ANY, bool LTOP = false>
-__device__ __forceinline__ bool traverseBin(const float4 *__restrict__ nodes, const float4 *__restrict__ tris, f3 o, f3 d,
-                                            float tmin, float &tmax, uint32_t &hitTri, float &hu, float &hv,
-                                            const TStack &stk, const float4 *lnodes = nullptr, int ntop = 0) {
-    const int DONE = 0x7fffffff;
-    const SlabRay sr = slabRay(o, d);
-    const f3 idir = sr.idir, aLo = sr.addLo, aHi = sr.addHi;
-    // rounding of the slab distances fma(plane, idir, -o * idir) is bounded by a few ulps of |o * idir|
-    const float tslack = sr.tslack;
-    int sp = 0;
-    int node = 0;   // >= 0 inner node, < 0 leaf ref, DONE
-    int leaf = 0;   // postponed leaf ref (< 0) or none (>= 0)
-    bool found = false;
-    while (node != DONE) {
-        // boxes are culled against tmax widened by the slab-distance rounding: a triangle that ties
-        // with the current hit (shared edge, coplanar) can sit in a box whose rounded entry distance
-        // lands just past tmax, and skipping it would make the tie-break (lower index) depend on
-        // traversal order, i.e. on which paths share the wave (box intervals: slabRay)
-        const float tcull = tmax * 1.000001f + tslack;
-        while (node >= 0 && node != DONE) {
-            float4 n0, n1, n2, n3;
-            if (LTOP && node < ntop) {
-                n0 = lnodes[4 * node + 0];
-                n1 = lnodes[4 * node + 1];
-                n2 = lnodes[4 * node + 2];
-                n3 = lnodes[4 * node + 3];
-            } else {
-                n0 = nodes[4 * node + 0];
-                n1 = nodes[4 * node + 1];
-                n2 = nodes[4 * node + 2];
-                n3 = nodes[4 * node + 3];
-            }
-            float a0 = fmaf(n0.x, idir.x, aLo.x), a1 = fmaf(n0.y, idir.x, aHi.x);
-            float a2 = fmaf(n0.z, idir.y, aLo.y), a3 = fmaf(n0.w, idir.y, aHi.y);
-            float a4 = fmaf(n2.x, idir.z, aLo.z), a5 = fmaf(n2.y, idir.z, aHi.z);
-            float c0min = fmaxf(fmaxf(fminf(a0, a1), fminf(a2, a3)), fmaxf(fminf(a4, a5), tmin));
-            float c0max = fminf(fminf(fmaxf(a0, a1), fmaxf(a2, a3)), fminf(fmaxf(a4, a5), tcull));
-            float b0 = fmaf(n1.x, idir.x, aLo.x), b1 = fmaf(n1.y, idir.x, aHi.x);
-            float b2 = fmaf(n1.z, idir.y, aLo.y), b3 = fmaf(n1.w, idir.y, aHi.y);
-            float b4 = fmaf(n2.z, idir.z, aLo.z), b5 = fmaf(n2.w, idir.z, aHi.z);
-            float c1min = fmaxf(fmaxf(fminf(b0, b1), fminf(b2, b3)), fmaxf(fminf(b4, b5), tmin));
-            float c1max = fminf(fminf(fmaxf(b0, b1), fmaxf(b2, b3)), fminf(fmaxf(b4, b5), tcull));
-            const bool h0 = c0min <= c0max * kBoxRel, h1 = c1min <= c1max * kBoxRel;
-            const int ch0 = __float_as_int(n3.x), ch1 = __float_as_int(n3.y);
-            if (!h0 && !h1) {
-                node = sp > 0 ? (int)stk.get(--sp) : DONE;
-            } else {
-                node = h0 ? ch0 : ch1;
-                if (h0 && h1) {
-                    int farC = ch1;
-                    if (c1min < c0min) {
-                        node = ch1;
-                        farC = ch0;
-                    }
-                    if (sp < STACK_DEPTH) stk.put(sp++, (uint32_t)farC);
-                }
-            }
-            // first leaf found: postpone it and keep descending
-            if (node < 0 && leaf >= 0) {
-                leaf = node;
-                node = sp > 0 ? (int)stk.get(--sp) : DONE;
-            }
-            if (!__any(leaf >= 0)) break;  // every lane still here holds a leaf
-        }
-        while (leaf < 0) {
-            const uint32_t lr = ~(uint32_t)leaf;
-            const uint32_t first = lr >> 4, cnt = lr & 15u;
-            for (uint32_t k = 0; k < cnt; ++k) {
-                const uint32_t tr = first + k;
-                float tt, bu, bv;
-                // equal distances (shared edges, coplanar triangles) go to the lower original triangle
-                // index (acceptHit), so the closest hit depends neither on the BVH nor on the order in
-                // which the wave's postponed leaves are visited (and thus on which paths share the wave)
-                if (triHit(tris, tr, o, d, tmin, tmax, tt, bu, bv) && acceptHit(tris, tt, tmax, tr, hitTri)) {
-                    found = true;
-                    if (ANY) return true;
-                    tmax = tt;
-                    hitTri = tr;
-                    hu = bu;  // weight of p1
-                    hv = bv;  // weight of p2
-                }
-            }
-            // another postponed leaf (in node)?  process it too
-            leaf = node;
-            if (node < 0) node = sp > 0 ? (int)stk.get(--sp) : DONE;
-        }
-    }
-    return found;
-}
-
-// the closest-hit walk of this build's closest-hit BVH (SceneDev::nodes)
-template <bool ANY, bool LTOP = false>
+// the closest-hit walk of the closest-hit BVH (SceneDev::nodes)
+template <bool ANY>
 __device__ __forceinline__ bool traverse(const float4 *__restrict__ nodes, const float4 *__restrict__ tris, f3 o, f3 d,
                                          float tmin, float &tmax, uint32_t &hitTri, float &hu, float &hv,
-                                         const TStack &stk, const float4 *lnodes = nullptr, int ntop = 0) {
-#if PG_BVH4
-    return traverse4<ANY, LTOP>(nodes, tris, o, d, tmin, tmax, hitTri, hu, hv, stk, lnodes, ntop);
-#else
-    return traverseBin<ANY, LTOP>(nodes, tris, o, d, tmin, tmax, hitTri, hu, hv, stk, lnodes, ntop);
-#endif
+                                         const TStack &stk) {
+    return traverse4<ANY>(nodes, tris, o, d, tmin, tmax, hitTri, hu, hv, stk);
 }
 
-// shadow-ray any hit: the 8-wide BVH, or the 4-wide closest-hit BVH in PG_SHADOW4 builds (A/B; the
-// 4-wide walk's stack is the wide stack's storage, >= LDS_STACK LDS words + the shared overflow ring)
-#ifndef PG_SHADOW4
-#define PG_SHADOW4 0
-#endif
-// tri: the BVH-order triangle the 8-wide walk accepted (~0: no hit; PG_SHADOW4 builds do not report it)
+// shadow-ray any hit: the 8-wide BVH
+// tri: the BVH-order triangle the 8-wide walk accepted (~0: no hit)
 __device__ __forceinline__ bool occluded(const SceneDev &sc, f3 o, f3 d, float tmin, float tmax, const WStack &w,
                                          uint32_t &tri) {
     tri = 0xFFFFFFFFu;
     float u, v;
-#if PG_BVH4 && PG_SHADOW4
-    uint32_t t4 = 0xFFFFFFFFu;
-    return traverse4<true>(sc.nodes, sc.tris, o, d, tmin, tmax, t4, u, v, TStack{w.lds, w.ovf, w.ostride});
-#else
     return traverseWide<true>(sc.wnodes, sc.wtris, o, d, tmin, tmax, tri, u, v, w);
-#endif
 }
 __device__ __forceinline__ bool occluded(const SceneDev &sc, f3 o, f3 d, float tmin, float tmax, const WStack &w) {
     uint32_t tri;

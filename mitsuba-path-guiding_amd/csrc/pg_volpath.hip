@@ -123,7 +123,6 @@ struct MedView {
     const float *density;
     const float *maj;
     int rx, ry, rz;
-    int bx, by;
     int mx, my, mz;
     f3 gs, go, lo, hi;
     float scale, invMax;
@@ -142,8 +141,6 @@ __device__ __forceinline__ MedView medView(const GMedium *media, int m) {
     v.scale = G.scale;
     v.invMax = G.invMax;
     v.maj = G.maj;
-    v.bx = (int)G.bx;
-    v.by = (int)G.by;
     v.mx = (int)G.mx;
     v.my = (int)G.my;
     v.mz = (int)G.mz;
@@ -159,28 +156,11 @@ __device__ __forceinline__ float lookupDensity(const MedView &M, f3 p) {
         return 0.0f;
 #endif
     const float fx = px - x1, fy = py - y1, fz = pz - z1, _fx = 1.0f - fx, _fy = 1.0f - fy, _fz = 1.0f - fz;
-#if PG_DENSITY_BRICKS
-    // per-axis (brick, in-brick) offsets of the two corner coordinates
-    const int x2 = x1 + 1, y2 = y1 + 1, z2 = z1 + 1;
-    const uint32_t ax1 = (uint32_t)((x1 >> 2) * 64 + (x1 & 3)), ax2 = (uint32_t)((x2 >> 2) * 64 + (x2 & 3));
-    const uint32_t ay1 = (uint32_t)((y1 >> 2) * M.bx * 64 + (y1 & 3) * 4), ay2 = (uint32_t)((y2 >> 2) * M.bx * 64 + (y2 & 3) * 4);
-    const uint32_t zs = (uint32_t)(M.bx * M.by * 64);
-    const uint32_t az1 = (uint32_t)(z1 >> 2) * zs + (uint32_t)(z1 & 3) * 16, az2 = (uint32_t)(z2 >> 2) * zs + (uint32_t)(z2 & 3) * 16;
-    const float *D = M.density;
-    const float d000 = D[az1 + ay1 + ax1], d001 = D[az1 + ay1 + ax2], d010 = D[az1 + ay2 + ax1], d011 = D[az1 + ay2 + ax2];
-    const float d100 = D[az2 + ay1 + ax1], d101 = D[az2 + ay1 + ax2], d110 = D[az2 + ay2 + ax1], d111 = D[az2 + ay2 + ax2];
-#elif PG_DENSITY_CORNERS
     const size_t cell = ((size_t)z1 * (size_t)(M.ry - 1) + (size_t)y1) * (size_t)(M.rx - 1) + (size_t)x1;
     const float4 *cp = reinterpret_cast<const float4 *>(M.density) + 2 * cell;
     const float4 lo = cp[0], hi = cp[1];
     const float d000 = lo.x, d001 = lo.y, d010 = lo.z, d011 = lo.w;
     const float d100 = hi.x, d101 = hi.y, d110 = hi.z, d111 = hi.w;
-#else
-    const size_t sy = (size_t)M.rx, sz = (size_t)M.rx * M.ry;
-    const float *b = M.density + (size_t)z1 * sz + (size_t)y1 * sy + x1;
-    const float d000 = b[0], d001 = b[1], d010 = b[sy], d011 = b[sy + 1];
-    const float d100 = b[sz], d101 = b[sz + 1], d110 = b[sz + sy], d111 = b[sz + sy + 1];
-#endif
     return ((d000 * _fx + d001 * fx) * _fy + (d010 * _fx + d011 * fx) * fy) * _fz +
            ((d100 * _fx + d101 * fx) * _fy + (d110 * _fx + d111 * fx) * fy) * fz;
 }
@@ -1142,12 +1122,12 @@ __device__ __forceinline__ void volEnd(const VolDev &v, uint32_t slot, const VPa
 }
 __device__ __forceinline__ uint32_t slotShard(uint32_t slot) { return (slot >> 6) & (PG_QSHARDS - 1); }
 
-// flight order key (PG_VOL_SORT; pg_layout.h PG_VOL_SORT_KEY): the Morton code of the cell of the medium's
-// box that holds o -- 8^3 cells (9 bits, 512 bins) or 16^3 (12 bits), or the direction octant and an
-// 8^3 cell -- so a sorted flight queue walks the density grid region by region
+// flight order key (PG_VOL_SORT; pg_layout.h PG_VOL_SORT_BINS): the Morton code of the cell of the medium's
+// box that holds o -- 8^3 cells (9 bits, 512 bins) -- so a sorted flight queue walks the density grid region
+// by region
 __device__ __forceinline__ uint16_t flightKey(const VolDev &v, int m, f3 o, f3 d) {
     const GMedium &M = v.media[m];
-    constexpr int bits = PG_VOL_SORT_KEY == 0 ? 4 : 3;
+    constexpr int bits = 3;
     constexpr float res = (float)(1 << bits);
     const float fx = (o.x - M.lo[0]) / (M.hi[0] - M.lo[0]), fy = (o.y - M.lo[1]) / (M.hi[1] - M.lo[1]),
                 fz = (o.z - M.lo[2]) / (M.hi[2] - M.lo[2]);
@@ -1156,27 +1136,19 @@ __device__ __forceinline__ uint16_t flightKey(const VolDev &v, int m, f3 o, f3 d
     uint32_t k = 0;
     for (int b = 0; b < bits; ++b)
         k |= (((cx >> b) & 1u) << (3 * b)) | (((cy >> b) & 1u) << (3 * b + 1)) | (((cz >> b) & 1u) << (3 * b + 2));
-    if (PG_VOL_SORT_KEY == 1) k |= ((d.x < 0 ? 1u : 0u) | (d.y < 0 ? 2u : 0u) | (d.z < 0 ? 4u : 0u)) << 9;
     return (uint16_t)k;
 }
-// surface vertices split by the hit triangle (PG_VOL_SPLIT_SURF): delta surfaces (the null boundaries of
-// media, smooth conductors and dielectrics: no emitter sample, no shadow walk), emitters (PG_VOL_SPLIT_EMIT:
+// surface vertices split by the hit triangle: delta surfaces (the null boundaries of
+// media, smooth conductors and dielectrics: no emitter sample, no shadow walk), emitters (VolDev::tcheap:
 // black in the scenes here, so the path ends there) and escaped rays go to their own queue, so the waves
 // of the other surfaces' shadow walks carry no idle lanes
-#ifndef PG_VOL_SPLIT_SURF
-#define PG_VOL_SPLIT_SURF 1
-#endif
-#ifndef PG_VOL_SPLIT_EMIT
-#define PG_VOL_SPLIT_EMIT 1
-#endif
 __device__ __forceinline__ bool cheapSurface(const SceneDev &sc, const VolDev &v, bool valid, uint32_t tri) {
-    return PG_VOL_SPLIT_SURF &&
-           (!valid || (PG_VOL_SPLIT_EMIT ? v.tcheap[tri] != 0 : (sc.tclass[tri] & PG_TCLASS_MASK) == PG_CLASS_DELTA));
+    return !valid || v.tcheap[tri] != 0;
 }
 __device__ __forceinline__ void surfAppend(bool pred, bool cheap, uint32_t slot, const Queue &qs, const Queue &qd,
                                            uint32_t sh) {
     waveAppend(pred && !cheap, slot, qs.items + (size_t)sh * qs.stride, qs.counts + sh);
-    if (PG_VOL_SPLIT_SURF) waveAppend(pred && cheap, slot, qd.items + (size_t)sh * qd.stride, qd.counts + sh);
+    waveAppend(pred && cheap, slot, qd.items + (size_t)sh * qd.stride, qd.counts + sh);
 }
 // append to a flight queue, with the order key when the queue carries keys
 __device__ __forceinline__ void flightAppend(bool pred, uint32_t slot, uint16_t key, const Queue &q, uint32_t sh) {

@@ -20,7 +20,6 @@ bool triHit(uint32_t tr, const float *o, const float *d, float tmin, float tmax,
     // the record's three rows, wherever PG_TRI_ROW puts them
     float w[12];
     for (uint32_t r = 0; r < 3; ++r) std::memcpy(&w[4 * r], &g_bvh.tris[4 * (size_t)PG_TRI_ROW(tr, r)], 16);
-#if PG_TRIACCEL
     // TriAccel::rayIntersect (triaccel.h:96-157), the device triHit's arithmetic (no contraction)
     uint32_t k;
     std::memcpy(&k, &w[3], 4);
@@ -32,29 +31,15 @@ bool triHit(uint32_t tr, const float *o, const float *d, float tmin, float tmax,
     if (!(u >= 0.0f)) return false;
     const float v = hu * w[8] + hv * w[9];
     return v >= 0.0f && u + v <= 1.0f;
-#else
-    const float dz = d[0] * w[0] + d[1] * w[1] + d[2] * w[2];
-    const float oz = w[3] - (o[0] * w[0] + o[1] * w[1] + o[2] * w[2]);
-    tt = oz / dz;
-    if (!(tt >= tmin && tt <= tmax)) return false;
-    const float a = (w[7] + o[0] * w[4] + o[1] * w[5] + o[2] * w[6]) + tt * (d[0] * w[4] + d[1] * w[5] + d[2] * w[6]);
-    if (!(a >= 0.0f && a <= 1.0f)) return false;
-    const float b = (w[11] + o[0] * w[8] + o[1] * w[9] + o[2] * w[10]) + tt * (d[0] * w[8] + d[1] * w[9] + d[2] * w[10]);
-    return b >= 0.0f && a + b <= 1.0f;
-#endif
 }
 
 // the device walks' accept rule (pg_trace.h acceptHit): smaller t, or a tie on the lower original id
 bool accept(float tt, float tmax, uint32_t tr, uint32_t best) {
     if (tt < tmax || best == 0xFFFFFFFFu) return true;
-#if PG_TRIACCEL
     uint32_t a, b;
     std::memcpy(&a, &g_bvh.tris[4 * (size_t)PG_TRI_ROW(tr, 2) + 2], 4);
     std::memcpy(&b, &g_bvh.tris[4 * (size_t)PG_TRI_ROW(best, 2) + 2], 4);
     return a < b;
-#else
-    return tr < best;
-#endif
 }
 
 const float *qnode(int32_t n) { return &g_bvh.nodes[(size_t)n * 4 * PG_QNODE_F4]; }
