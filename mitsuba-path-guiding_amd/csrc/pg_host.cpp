@@ -140,7 +140,7 @@ struct Lane {
     uint32_t P = 0;
     int vtx_slots = 0;
     uint32_t vtxP = 0;  // slot stride of vtx (recording passes only allocate it)
-    DevBuf ray_o, ray_d, hit, thr, rad, pinfo, sh_d, sh_c, vtx, q0, q1, qs, qp, class_q, counters, stack_ovf;
+    DevBuf ray, hit, rad, vst, sh_d, sh_c, vtx, q0, q1, qs, qp, class_q, counters, stack_ovf;
     DevBuf qkey, qsorted, rsort_hist;  // ray-sorted trace queues (PG_RAY_SORT): keys, sorted entries, histograms
     bool sorted = false;               // the queue of the next trace launch is qsorted
     DevBuf tail_stats;                 // k_tail counters of the running chunk (kTailStats u64), copied to h_tail
@@ -522,8 +522,7 @@ SDDev sdView(const Ctx *c) {
     return s;
 }
 PathDev pathView(const Lane *c) {
-    return PathDev{c->ray_o.as<float4>(), c->ray_d.as<float4>(), c->hit.as<float4>(), c->thr.as<float4>(),
-                   c->rad.as<float4>(),   c->pinfo.as<uint4>(),
+    return PathDev{c->ray.as<float4>(),   c->hit.as<float4>(),   c->rad.as<float4>(), c->vst.as<uint4>(),
                    c->sh_d.as<float4>(),  c->sh_c.as<float4>(),  c->vtx.as<float4>(), c->stack_ovf.as<uint32_t>(),
                    c->P,                  c->vtxP,               c->aov.as<float4>()};
 }
@@ -620,7 +619,7 @@ int vertexSlots(const Ctx *c, bool rec) { return rec ? std::max(0, std::min(c->c
 void releasePaths(Ctx *c) {
     for (int li = 0; li < c->nlanes; ++li) {
         Lane &l = c->lanes[li];
-        for (DevBuf *b : {&l.ray_o, &l.ray_d, &l.hit, &l.thr, &l.rad, &l.pinfo, &l.sh_d, &l.sh_c,
+        for (DevBuf *b : {&l.ray, &l.hit, &l.rad, &l.vst, &l.sh_d, &l.sh_c,
                           &l.vtx, &l.q0, &l.q1, &l.qs, &l.qp, &l.class_q, &l.aov, &l.qkey, &l.qsorted})
             b->release();
         l.P = 0;
@@ -659,12 +658,10 @@ pg_status ensurePaths(Ctx *c, uint32_t want, bool rec) {
         if (want <= l.P && !aovMissing) continue;
         const uint32_t P = std::max(want, l.P);
         size_t f4 = (size_t)P * 16;
-        HIPC(c, l.ray_o.alloc(f4));
-        HIPC(c, l.ray_d.alloc(f4));
+        HIPC(c, l.ray.alloc(2 * f4));
         HIPC(c, l.hit.alloc(f4));
-        HIPC(c, l.thr.alloc(f4));
         HIPC(c, l.rad.alloc(f4));
-        HIPC(c, l.pinfo.alloc(f4));
+        HIPC(c, l.vst.alloc(2 * f4));
         HIPC(c, l.sh_d.alloc(f4));
         HIPC(c, l.sh_c.alloc(f4));
         const size_t qbytes = (size_t)PG_QSHARDS * pg_queue_stride(P) * 4;
@@ -2204,7 +2201,7 @@ pg_status renderVolpath(Ctx *c, uint32_t spp, uint32_t sample_offset, bool rec) 
     pv.vtx = v.vtx;
     pv.P = want;
     pv.vtxP = want;
-    pv.pinfo = nullptr;  // k_commit reads the vertex count from rad[item].w
+    pv.vst = nullptr;  // k_commit reads the vertex count from rad[item].w
     const uint32_t layersPer = std::max<uint32_t>(1, want / npix), pixPer = std::min(npix, want);
     std::vector<VChunk> chunks;
     for (uint32_t layer = 0; layer < spp;) {
@@ -2347,7 +2344,7 @@ static pg_status renderPass(Ctx *c, uint32_t spp, uint32_t sample_offset, int32_
             size_t held = 0;
             for (int li = 0; li < c->nlanes; ++li) {
                 const Lane &l = c->lanes[li];
-                for (const DevBuf *b : {&l.ray_o, &l.ray_d, &l.hit, &l.thr, &l.rad, &l.pinfo,
+                for (const DevBuf *b : {&l.ray, &l.hit, &l.rad, &l.vst,
                                         &l.sh_d, &l.sh_c, &l.vtx, &l.q0, &l.q1, &l.qs, &l.qp, &l.class_q, &l.aov})
                     held += b->bytes;
             }

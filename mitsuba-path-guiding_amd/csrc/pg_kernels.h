@@ -41,9 +41,10 @@ struct SceneDev {
 // (T before the vertex, p_guide(wo) or -1 when the vertex was not guided)
 #define PG_VTX_F4 4
 struct PathDev {
-    float4 *ray_o, *ray_d, *hit, *thr, *rad;  // row meanings: pg_layout.h "Path state"
-    uint4 *pinfo;
-    float4 *sh_d, *sh_c;  // shadow ray (direction, tmax) and contribution; its origin is ray_o
+    float4 *ray;       // 32-B ray record per slot: pathRayO, pathRayD below (pg_layout.h "Path state")
+    float4 *hit, *rad;
+    uint4 *vst;        // 32-B vertex-state record per slot: pathInfo, pathThr below
+    float4 *sh_d, *sh_c;  // shadow ray (direction, tmax) and contribution; its origin is the ray record's
     float4 *vtx;       // [max_vertices][P][PG_VTX_F4]
     uint32_t *stack_ovf;  // traversal-stack overflow ring, pg_stack_overflow_words(0) words
     uint32_t P;        // path-state capacity
@@ -52,6 +53,13 @@ struct PathDev {
     // written by the chunk's first k_trace; k_film turns it into albedo + normal sums.  nullptr: off.
     float4 *aov;
 };
+// the rows of a slot's records: no kernel indexes ray or vst by hand
+__host__ __device__ inline float4 *pathRayO(const PathDev &p, uint32_t slot) { return p.ray + 2 * (size_t)slot; }
+__host__ __device__ inline float4 *pathRayD(const PathDev &p, uint32_t slot) { return p.ray + 2 * (size_t)slot + 1; }
+__host__ __device__ inline uint4 *pathInfo(const PathDev &p, uint32_t slot) { return p.vst + 2 * (size_t)slot; }
+__host__ __device__ inline float4 *pathThr(const PathDev &p, uint32_t slot) {
+    return reinterpret_cast<float4 *>(p.vst + 2 * (size_t)slot + 1);
+}
 
 struct SDDev {
     const uint2 *snodes;
@@ -242,7 +250,7 @@ void pg_launch_envmap_query(hipStream_t s, const SceneDev &sc, int op, const flo
 // (n x 3) with refN = 0 and samples smp (n x 2); out n x 8
 void pg_launch_emitter_query(hipStream_t s, const GParams &g, const SceneDev &sc, const float *ref, const float *smp,
                              uint32_t n, float *out);
-// p.pinfo == nullptr: the vertex count of slot i is bits(p.rad[i].w) (volpath items)
+// p.vst == nullptr: the vertex count of slot i is bits(p.rad[i].w) (volpath items)
 // env_hits: surface path with an environment emitter (escape radiance in the hit record)
 void pg_launch_commit(hipStream_t s, const PathDev &p, uint32_t nslots, int max_vertices, pg_record *records,
                       unsigned long long *rec_count, unsigned long long rec_capacity, int env_hits);

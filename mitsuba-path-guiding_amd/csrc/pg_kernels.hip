@@ -35,14 +35,14 @@ __global__ __launch_bounds__(256) void k_camera(GParams g, PathDev p, const uint
     f3 o, wd;
     float tmin, tmax;
     cameraRay<LENS>(g, pix, rngKey(pix, g.seed), sample, o, wd, tmin, tmax);
-    stS(&p.ray_o[slot], f4(o, tmin));
-    stS(&p.ray_d[slot], f4(wd, tmax));
+    stS(pathRayO(p, slot), f4(o, tmin));
+    stS(pathRayD(p, slot), f4(wd, tmax));
     // throughput (1, eta 1) is implied by depth 1: the first bounce's readers (shadeOne, envEscapeRadiance) do not
     // load it.  ray_d.w is the far clip along the ray; a bounce ray keeps woPdf there (pg_layout.h "Path state").
     // L = 0 is stored: a camera ray that escapes is
     // never shaded and k_film reads its L.
     stS(&p.rad[slot], make_float4(0.f, 0.f, 0.f, 0.f));
-    stS(&p.pinfo[slot], make_uint4(pix, sample, 1u | (PF_EMITTED_QUERY << 16), 0u));
+    stS(pathInfo(p, slot), make_uint4(pix, sample, 1u | (PF_EMITTED_QUERY << 16), 0u));
     if (banded) {  // pg_kernels.h pg_banded_shard_count: band r of the local pixels -> shards r, r + 8, ...
         const uint32_t r = (uint32_t)(((uint64_t)lp * 8u) / npix);
         const uint32_t b0 = pg_band_start(r, npix), m = pg_band_start(r + 1, npix) - b0;
@@ -87,7 +87,7 @@ __device__ __forceinline__ f3 envEscapeRadiance(const GParams &g, const SceneDev
         if (!(flags & PF_EMITTED_QUERY) || (g.hide_emitters && !(flags & PF_SCATTERED))) return mk1(0.f);
         add = envEval(*sc.env, rd);
     } else {
-        const float4 T4 = p.thr[slot];
+        const float4 T4 = ldS(pathThr(p, slot));
         if (g.hide_emitters && !(flags & PF_SCATTERED)) return mk1(0.f);
         float w = 1.0f;
         if (g.use_nee) {
@@ -172,7 +172,7 @@ __device__ __forceinline__ void traceRows(const GParams &g, const SceneDev &sc, 
         uint32_t slot = 0;
         if (i < n) {
             slot = items[i];
-            float4 o = ldS(&p.ray_o[slot]), d = ldS(&p.ray_d[slot]);
+            float4 o = ldS(pathRayO(p, slot)), d = ldS(pathRayD(p, slot));
             // the doomed bit rides through the walk in the slot's top bit (slots are < 2^31): no register of its own
             // under k_rays' 64-VGPR cap
             slot |= rayDoomed(o) ? 0x80000000u : 0u;
@@ -186,7 +186,7 @@ __device__ __forceinline__ void traceRows(const GParams &g, const SceneDev &sc, 
             float4 hr = make_float4(h ? tmax : 0.0f, __uint_as_float(h ? tri : 0xFFFFFFFFu), u, v);
             if (first) first[slot] = hr;
             if (ENV && !h) {
-                const f3 e = envEscapeRadiance(g, sc, p, slot, xyz(d), CAM ? kCameraWord : p.pinfo[slot].z, d.w);
+                const f3 e = envEscapeRadiance(g, sc, p, slot, xyz(d), CAM ? kCameraWord : pathInfo(p, slot)->z, d.w);
                 hr = make_float4(e.x, hr.y, e.y, e.z);
             }
             cls = hitClass(sc, h, tri, doomed, hr);
@@ -243,7 +243,7 @@ __device__ __forceinline__ void shadowRows(const SceneDev &sc, const PathDev &p,
             uint32_t tri = 0xFFFFFFFFu;
             if (i < n) {
                 const uint32_t slot = items[i];
-                const float4 o = ldS(&p.ray_o[slot]), d = ldS(&p.sh_d[slot]);
+                const float4 o = ldS(pathRayO(p, slot)), d = ldS(&p.sh_d[slot]);
                 if (!occluded(sc, xyz(o), xyz(d), shadowTmin(o), d.w, stk, tri)) shadowAdd(p, slot);
             }
             if (blockerRowCounted(base / TRACE_BLOCK)) {  // pg_layout.h PG_BLOCKER_SAMPLE
@@ -257,7 +257,7 @@ __device__ __forceinline__ void shadowRows(const SceneDev &sc, const PathDev &p,
     for (uint32_t i = (bid / PG_QSHARDS) * TRACE_BLOCK + threadIdx.x; i < n; i += nblk / PG_QSHARDS * TRACE_BLOCK) {
         uint32_t slot = items[i];
         // the shadow ray starts at the shading point, which is also the extension ray's origin
-        float4 o = ldS(&p.ray_o[slot]), d = ldS(&p.sh_d[slot]);
+        float4 o = ldS(pathRayO(p, slot)), d = ldS(&p.sh_d[slot]);
         if (!occluded(sc, xyz(o), xyz(d), shadowTmin(o), d.w, stk)) shadowAdd(p, slot);
     }
 }
@@ -289,7 +289,7 @@ __device__ __forceinline__ void probeRows(const SceneDev &sc, const PathDev &p, 
     uint32_t hits = 0, misses = 0;
     for (uint32_t i = (bid / PG_QSHARDS) * TRACE_BLOCK + threadIdx.x; i < n; i += nblk / PG_QSHARDS * TRACE_BLOCK) {
         const uint32_t slot = items[i];
-        if (probeHit(sc, ldS(&p.ray_o[slot]), ldS(&p.ray_d[slot]), stk)) ++hits;
+        if (probeHit(sc, ldS(pathRayO(p, slot)), ldS(pathRayD(p, slot)), stk)) ++hits;
         else ++misses;
     }
     for (int off = 32; off > 0; off >>= 1) {
@@ -427,16 +427,16 @@ __device__ __forceinline__ void shadeOne(const GParams &g, const SceneDev &sc, c
     bool watched = false;
 #endif
     do {
-        const uint4 pi = ldS(&p.pinfo[slot]);
+        const uint4 pi = ldS(pathInfo(p, slot));
         const uint32_t pix = pi.x, sample = pi.y;
 #if PG_WATCH
         watched = pix == pgWatch[0] && sample == pgWatch[1];
 #endif
-        const float4 rd4 = ldS(&p.ray_d[slot]);
+        const float4 rd4 = ldS(pathRayD(p, slot));
         float4 hv = ldS(&p.hit[slot]);
         uint32_t depth = pi.z & 0xFFFFu, flags = pi.z >> 16, nv = pi.w;
         // a camera ray's state is implied (k_camera stores no throughput)
-        float4 T4 = depth == 1 ? make_float4(1.f, 1.f, 1.f, 1.f) : ldS(&p.thr[slot]);
+        float4 T4 = depth == 1 ? make_float4(1.f, 1.f, 1.f, 1.f) : ldS(pathThr(p, slot));
         f3 T = xyz(T4);
         // L is loaded where the vertex first needs it: before it adds emission or snapshots a training vertex.  Most
         // vertices of a non-recording pass do neither, and the dirtyL store below is the only one either way.
@@ -667,7 +667,7 @@ __device__ __forceinline__ void shadeOne(const GParams &g, const SceneDev &sc, c
                 const float tmin = pg_ray_tmin(h.p.x, h.p.y, h.p.z);
                 const float etaN = eta * bs.eta;
                 // the next vertex's exits, decided here (PF_DOOMED): its depth tests, and its roulette draw against
-                // the throughput and eta it will load from thr[slot]
+                // the throughput and eta it will load from its vst record
                 bool doomed = false;
                 if (cull) {
                     const uint32_t D = depth + 1;
@@ -681,27 +681,27 @@ __device__ __forceinline__ void shadeOne(const GParams &g, const SceneDev &sc, c
                     probe = pg_ray_misses_boxes(sc.em_box, sc.num_em_boxes, sc.em_absmax, po, pd, tmin);
                 }
                 // the bounce ray's rows (pg_layout.h "Path state")
-                stS(&p.ray_o[slot], f4(h.p, doomed ? -tmin : tmin));
-                stS(&p.ray_d[slot], f4(wo, woPdf));
+                stS(pathRayO(p, slot), f4(h.p, doomed ? -tmin : tmin));
+                stS(pathRayD(p, slot), f4(wo, woPdf));
                 if (probe) {  // the path ends here: the hit record a culled hit gets, no state for a next vertex
                     stS(&p.hit[slot], make_float4(0.0f, __uint_as_float(0xFFFFFFFFu), 0.0f, 0.0f));
                 } else {
-                    stS(&p.thr[slot], f4(Tn, etaN));
+                    stS(pathThr(p, slot), f4(Tn, etaN));
                     flags = (flags & ~(PF_EMITTED_QUERY | PF_PREV_DELTA | PF_PREV_FRONT)) |
                         ((bs.type & EDelta) ? PF_PREV_DELTA : 0u) | (doomed ? PF_DOOMED : 0u) |
                         (pg_prev_front(wo.x, wo.y, wo.z, refN.x, refN.y, refN.z) ? PF_PREV_FRONT : 0u);
-                    stPinfoZW(&p.pinfo[slot], (depth + 1) | (flags << 16), nv);
+                    stPinfoZW(pathInfo(p, slot), (depth + 1) | (flags << 16), nv);
                     alive = true;
                     if (wantKey) rkey = rayOrderKey(sd, h.p, wo);
                 }
             }
         }
         if (shadow) {  // origin: ray_o (the extension ray's, written above when the path goes on)
-            if (!alive && !probe) stS(&p.ray_o[slot], f4(h.p, 0.0f));
+            if (!alive && !probe) stS(pathRayO(p, slot), f4(h.p, 0.0f));
             stS(&p.sh_d[slot], f4(neeD, neeDist * (1 - kShadowEpsilon)));
             stS(&p.sh_c[slot], f4(neeC, __uint_as_float(vtxIndex)));
         }
-        if (!alive && nv != pi.w) stPinfoZW(&p.pinfo[slot], pi.z, nv);
+        if (!alive && nv != pi.w) stPinfoZW(pathInfo(p, slot), pi.z, nv);
     } while (false);
     if (dirtyL) stS(&p.rad[slot], f4(L, 0.0f));
 #if PG_WATCH
@@ -944,7 +944,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PG_
             }
             if (shadow) {  // shadowRows for this path
                 ++shadows;
-                const float4 o = ldS(&p.ray_o[slot]), d = ldS(&p.sh_d[slot]);
+                const float4 o = ldS(pathRayO(p, slot)), d = ldS(&p.sh_d[slot]);
                 uint32_t btri;
                 const bool occ = occluded(sc, xyz(o), xyz(d), shadowTmin(o), d.w, wstk, btri);
                 if (COUNT && blockerRowCounted(i / TRACE_BLOCK)) {
@@ -964,7 +964,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PG_
                 }
             }
             if (!ENV && probe) {  // probeRows for this path: its last segment, a culled hit or an escape
-                const float4 o = ldS(&p.ray_o[slot]), d = ldS(&p.ray_d[slot]);
+                const float4 o = ldS(pathRayO(p, slot)), d = ldS(pathRayD(p, slot));
                 ++segs;
                 ++probes;
                 if (probeHit(sc, o, d, stk)) ++culled;
@@ -972,13 +972,13 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PG_
             }
             if (!alive) break;
             // traceRows for this path
-            const float4 o = ldS(&p.ray_o[slot]), d = ldS(&p.ray_d[slot]);
+            const float4 o = ldS(pathRayO(p, slot)), d = ldS(pathRayD(p, slot));
             float tmax = __builtin_huge_valf(), u = 0, v = 0;
             tri = 0xFFFFFFFFu;
             const bool h = traverse<false>(sc.nodes, sc.tris, xyz(o), xyz(d), fabsf(o.w), tmax, tri, u, v, stk);
             float4 hr = make_float4(h ? tmax : 0.0f, __uint_as_float(h ? tri : 0xFFFFFFFFu), u, v);
             if (ENV && !h) {
-                const f3 e = envEscapeRadiance(g, sc, p, slot, xyz(d), p.pinfo[slot].z, d.w);
+                const f3 e = envEscapeRadiance(g, sc, p, slot, xyz(d), pathInfo(p, slot)->z, d.w);
                 hr = make_float4(e.x, hr.y, e.y, e.z);
             }
             const int cls = hitClass(sc, h, tri, rayDoomed(o), hr);
@@ -1173,7 +1173,7 @@ __global__ __launch_bounds__(256) void k_commit(PathDev p, uint32_t nslots, int 
                                                 unsigned long long capacity, int env_hits) {
     uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t nv = 0;
-    if (slot < nslots) nv = min(p.pinfo ? p.pinfo[slot].w : __float_as_uint(p.rad[slot].w), (uint32_t)maxV);
+    if (slot < nslots) nv = min(p.vst ? pathInfo(p, slot)->w : __float_as_uint(p.rad[slot].w), (uint32_t)maxV);
     // wave inclusive scan of nv
     int lane = threadIdx.x & 63;
     uint32_t incl = nv;

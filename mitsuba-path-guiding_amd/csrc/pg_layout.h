@@ -221,11 +221,17 @@ inline void pg_qnode_box(const float *node, int s, float lo[3], float hi[3]) {
 #define PG_TCLASS_EMITTER 0x80u
 #define PG_TCLASS_MASK 0x7Fu
 
-// Path state of the surface wavefront, one 16-B row per slot and array (PathDev, pg_kernels.h):
+// Path state of the surface wavefront, 16-B rows per slot (PathDev, pg_kernels.h).  The rows that are always touched
+// together are the halves of one 32-B record, so a slot of a sparse wave costs one sector for both (DESIGN.md
+// section 5 "Paired state"); hit, rad, sh_d and sh_c are arrays of their own, one row per slot:
+//   ray[2 slot] = ray_o, ray[2 slot + 1] = ray_d     (pathRayO, pathRayD)
+//   vst[2 slot] = pinfo, vst[2 slot + 1] = thr       (pathInfo, pathThr)
 //   camera ray (k_camera):  ray_o = (camera position, near clip along the ray)   ray_d = (direction, far clip)
-//                           pinfo = (pixel, sample, 1 | PF_EMITTED_QUERY << 16, 0)   rad = 0   thr: implied (1, eta 1)
+//                           pinfo = (pixel, sample, 1 | PF_EMITTED_QUERY << 16, 0)   rad = 0   thr: implied (1, eta 1),
+//                           its half of the record keeps what the slot's previous path left there
 //   bounce ray (shadeOne):  ray_o = (p, +-tmin)   ray_d = (wo, woPdf)   thr = (T, eta)
-//                           pinfo.zw = (depth | flags << 16, training-vertex count), an 8-B store
+//                           pinfo.zw = (depth | flags << 16, training-vertex count), an 8-B store: with thr one
+//                           contiguous 24-B span of the vst record
 // A bounce ray's tmax is +inf, so the tracers take it as a constant (their CAM template flag tells camera rows from
 // bounce rows) and ray_d.w carries woPdf, the solid-angle pdf wo was sampled with.  It is read only by a vertex that
 // lands on an emitter and by an escape into the environment emitter, for the MIS weight against next-event
