@@ -1,12 +1,7 @@
-// Host driver behind the C-ABI (include/pg_capi.h): device context, scene flattening/upload,
-// the progressive pass driver (ProgressiveMonteCarloIntegrator::renderSamples/renderBlock,
-// src/librender/progressiveintegrator.cpp:65-114,222-282, re-expressed as a GPU wavefront loop),
-// training-record management and the SD-tree refit hook (postprogression, :314-317).
-#include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
-
+// Host driver behind the C-ABI (include/pg_capi.h): device context (pg_ctx.h), scene flattening/upload,
+// the query entry points, training-record management, the SD-tree refit hook (postprogression,
+// src/librender/progressiveintegrator.cpp:314-317) and RCCL.  The pass drivers live in pg_pass.cpp.
 #include <algorithm>
-#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -16,35 +11,20 @@
 #include <string>
 #include <vector>
 
-#include "../../include/pg_capi.h"
 #include "pg_bvh.h"
+#include "pg_ctx.h"
 #include "pg_envmap.h"
-#include "pg_kernels.h"
-#include "pg_layout.h"
 #include "pg_rtrans.h"
-#include "pg_sdtree.h"
 
-namespace {
+namespace pgh __attribute__((visibility("hidden"))) {
 
 constexpr uint32_t kStackDepth = 48;  // must match STACK_DEPTH in pg_kernels.hip
-constexpr uint32_t kMaxBounces = 1100;     // > gpu_depth_cap default (1024) + 2
-// per-bounce device counters (words): [0, 64) shard counts of the live queue entering the bounce,
-// [64, 128) shadow-queue shard counts, [128, 704) shard counts of the PG_NUM_CLASSES material-class
-// queues followed by the escaped-ray and the culled-hit counts (PG_CLASS_ROWS rows), [704, 768) shard counts of the
-// probe queue the bounce's shading fills (pg_layout.h "Doom probe"), [768, 832) the dropped shadow rays
-constexpr uint32_t kBounceWords = 832;
-constexpr uint32_t kShadowCounts = PG_QSHARDS, kClassCounts = 2 * PG_QSHARDS;
-constexpr uint32_t kProbeCounts = kClassCounts + PG_CLASS_ROWS * PG_QSHARDS;
-// shadow rays the shader resolved against the blocker list (Queue::dropped of the shadow queue)
-constexpr uint32_t kDropCounts = kProbeCounts + PG_QSHARDS;
-static_assert(kDropCounts + PG_QSHARDS <= kBounceWords, "counter layout");
-constexpr uint32_t kCounterWords = kBounceWords * (kMaxBounces + 1);
 // the device's bounce cap (GParams::depth_cap): max_depth + 1 or gpu_depth_cap.  The surface path keeps
 // one counter block per bounce, so its cap is at most kMaxBounces - 2 (pg_create rejects a larger
 // max_depth and clamps gpu_depth_cap there), and the bounce-by-bounce loop (maxBounces = depth_cap + 2 <=
 // kMaxBounces) and k_tail, which loops until shadeOne's depth_cap test ends the path, stop at the same
 // bounce.  The volumetric path has no per-bounce buffer and honours max_depth exactly.
-static uint32_t deviceDepthCap(const pg_config &cfg) {
+uint32_t deviceDepthCap(const pg_config &cfg) {
     const int64_t cap = cfg.max_depth > 0 ? (int64_t)cfg.max_depth + 1 : (int64_t)cfg.gpu_depth_cap;
     if (cfg.integrator == PG_INTEGRATOR_VOLPATH) return (uint32_t)std::min<int64_t>(cap, 0x7fffffff);
     return (uint32_t)std::min<int64_t>(cap, (int64_t)kMaxBounces - 2);
@@ -62,239 +42,9 @@ int materialClass(uint32_t model) {
     }
 }
 
-struct DevBuf {
-    void *p = nullptr;
-    size_t bytes = 0;
-    ~DevBuf() { release(); }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-    }
-    hipError_t alloc(size_t n) {
-        if (n <= bytes && p) return hipSuccess;
-        release();
-        if (n == 0) return hipSuccess;
-        hipError_t e = hipMalloc(&p, n);
-        if (e == hipSuccess) bytes = n;
-        else p = nullptr;
-        return e;
-    }
-    // growth with headroom, for buffers re-sized every training iteration (SD-tree): freeing and
-    // re-allocating device memory per refit stalled the next stream operation by up to ~20 ms
-    hipError_t grow(size_t n) {
-        if (n <= bytes && p) return hipSuccess;
-        return alloc(std::max(n, bytes + bytes / 2));
-    }
-    template <class T> T *as() const { return reinterpret_cast<T *>(p); }
-};
-
-// Pinned host staging buffer (reused): pageable-memory copies are pinned on demand by the runtime.
-struct PinnedBuf {
-    void *p = nullptr;
-    size_t bytes = 0;
-    ~PinnedBuf() {
-        if (p) (void)hipHostFree(p);
-    }
-    hipError_t reserve(size_t n) {
-        if (n <= bytes) return hipSuccess;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        bytes = 0;
-        n = std::max(n, (size_t)1 << 20);
-        n += n / 2;
-        hipError_t e = hipHostMalloc(&p, n, hipHostMallocDefault);
-        if (e == hipSuccess) bytes = n;
-        return e;
-    }
-};
-
-struct EventPair {
-    hipEvent_t a = nullptr, b = nullptr;
-};
-// what a timed launch ran (pg_stats buckets)
-enum LaunchKind { KT_TRACE = 0, KT_SHADE = 1, KT_SHADOW = 2, KT_RAYS = 3 };
-
-// One in-flight chunk of paths: its own stream, path state, queues and counters.  pg_render_pass
-// interleaves pg_config.path_lanes lanes, so while the host waits for one lane's per-bounce class counts the
-// GPU runs the other lane's kernels (and a lane's sparse late bounces overlap the other's).
-#define PG_MAX_LANES 4
-#ifndef PG_SMALL_PASS
-#define PG_SMALL_PASS (1u << 21)  // paths: passes up to this size run as one chunk (0: always one per lane)
-#endif
-// the same threshold at run time (A/B: PG_SMALL_PASS_PATHS overrides)
-uint64_t smallPass() {
-    static const uint64_t n = [] {
-        const char *e = std::getenv("PG_SMALL_PASS_PATHS");
-        return e ? (uint64_t)std::strtoull(e, nullptr, 10) : (uint64_t)PG_SMALL_PASS;
-    }();
-    return n;
-}
 #ifndef PG_PIXEL_BLOCK
 #define PG_PIXEL_BLOCK 8  // local pixel order inside a tile: 8x8 blocks (0: row-major)
 #endif
-#define PG_DEFAULT_LANES 3
-constexpr size_t kTailStats = 6;  // k_tail: segments, escaped, shadow rays, culled, probes, blocker-resolved shadow rays
-struct Lane {
-    hipStream_t stream = nullptr;
-    uint32_t P = 0;
-    int vtx_slots = 0;
-    uint32_t vtxP = 0;  // slot stride of vtx (recording passes only allocate it)
-    DevBuf ray, hit, rad, vst, sh_d, sh_c, vtx, q0, q1, qs, qp, class_q, counters, stack_ovf;
-    DevBuf qkey, qsorted, rsort_hist;  // ray-sorted trace queues (PG_RAY_SORT): keys, sorted entries, histograms
-    bool sorted = false;               // the queue of the next trace launch is qsorted
-    DevBuf tail_stats;                 // k_tail counters of the running chunk (kTailStats u64), copied to h_tail
-    uint64_t *h_tail = nullptr;        // pinned: k_tail counters of the last finished chunk
-    DevBuf aov;  // denoiser features per slot (pg_config.aovs), 2 x float4
-    uint32_t *h_counts = nullptr;  // pinned: per-bounce class counts of the running chunk
-    uint32_t *h_stats = nullptr;   // pinned: counters of the last finished chunk
-    std::vector<EventPair> ev[2];  // kernel-timing events: running chunk / last finished chunk
-    std::vector<uint8_t> evkind[2];  // LaunchKind of each used pair
-    size_t evused[2] = {0, 0};
-    int evcur = 0;
-    hipEvent_t ready = nullptr;    // class counts of the current bounce are on the host
-    hipEvent_t done = nullptr;     // last finished chunk's statistics copy
-    bool stats_pending = false;
-    uint32_t stats_bounces = 0;
-    // PG_DEBUG_COUNTS: per-bounce segment totals the host read (running chunk / last finished chunk),
-    // checked against the device counters of the finished chunk
-    std::vector<uint64_t> used_cur, used_prev;
-    // running chunk
-    bool active = false;
-    bool traced = false;  // every path of the chunk terminated; film waits for its turn
-    uint32_t chunk = 0;   // chunk index within the pass (films accumulate in this order)
-    uint32_t b = 0, bound = 0, n = 0, pb = 0, np = 0, nl = 0, layer0 = 0;
-};
-
-// One in-flight chunk of the volumetric wavefront (renderVolpath): its own stream, SoA path state
-// (VolWave, 7 x 16 B per slot), five sharded queues (flight / surface for two iterations, medium
-// vertices) with their counters and host copy, per-item radiance and stack overflow ring.  Several
-// lanes overlap one chunk's sparse late iterations and k_vtail with the next chunk's full ones.
-struct VolLane {
-    hipStream_t stream = nullptr;
-    hipEvent_t ready = nullptr;  // the counters' host copy landed
-    // the deferred transmittance walks (k_vnee) on a stream of their own, overlapping the next iteration's
-    // free flights (PG_VOL_NEE_OVERLAP): vdone = this iteration's interactions done, ndone = its walks done
-    hipStream_t nstream = nullptr;
-    hipEvent_t vdone = nullptr, ndone = nullptr;
-    bool npending = false;
-    DevBuf state, items, counts, rad, ovf;
-    DevBuf keys, sorted, hist;  // flight order keys of both flight queues, a sorted copy, histograms (PG_VOL_SORT)
-    PinnedBuf host;
-    uint32_t cap = 0;
-    int stateF4 = 0;  // float4 arrays per slot in `state` (7, or 14 with the k_vnee stage's records)
-    // the chunk in flight
-    bool active = false, waved = false;  // waved: its paths are done, its film waits for its turn
-    uint32_t chunk = 0, pb = 0, np = 0, nl = 0, sample_base = 0;
-    int it = 0;
-    EventPair span;                      // chunk start .. film (pg_stats volume_ms; moved to the pass's list)
-};
-
-struct Ctx {
-    pg_config cfg{};
-    std::string err;
-    std::atomic<bool> cancel{false};
-    hipStream_t stream = nullptr;
-    // scene
-    bool has_scene = false;
-    GParams g{};
-    DevBuf nodes, tris, wnodes, tshade, tclass, mats, rtab, ems, emtri, emcdf;  // tris: both BVHs' triangles
-    DevBuf env, envtex, envtab;  // environment emitter: GEnv record, texels, CDFs + row weights
-    bool has_env = false;
-    // media (volpath)
-    DevBuf media, density, tmed, majorant, tcheap;
-    bool diffuse_null = false;  // every material diffuse or null: VolDev::models (PG_VOL_MODELS=0 turns it off)
-    int32_t cam_medium = -1;
-    uint32_t num_media = 0;
-    DevBuf vol_rad, vol_ovf, vol_work;  // per-item radiance, traversal-stack overflow, counter + stats
-    DevBuf vol_vtx;                     // guided volpath training vertices (48 B each)
-    uint64_t vol_vtx_cap = 0;
-    // volumetric wavefront (PG_VOL_WAVEFRONT) lanes
-    VolLane vlanes[PG_MAX_LANES];
-    hipEvent_t vw_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // stage timing (kernel_timing)
-    uint32_t vol_cap = 0;
-    uint32_t num_tris = 0, num_mats = 0;
-    uint32_t bvh_top_nodes = 0;  // breadth-first top levels of the 4-wide BVH (SceneDev::top_nodes: no reader)
-    // padded boxes over the emitter triangles (pg_layout.h "Doom probe"): SceneDev::em_box
-    uint32_t num_em_boxes = 0;
-    float em_absmax = 0.0f;
-    float em_box[PG_EMBOX_MAX][6] = {};
-    // shadow blockers (pg_layout.h "Shadow blockers"): the per-triangle counts of the recording passes and the list
-    // chosen from them (SceneDev::blk); both empty after an upload and after pg_put_sdtree (a new job)
-    DevBuf blk_counts;
-    PinnedBuf h_blk_counts;     // the counts' host copy (learnBlockers)
-    std::vector<float> host_tris, host_shade;  // host copies of tris and tshade: the listed triangles' records
-    bool blk_stopped = false;   // no more counting in this job, the list stays (learnBlockers)
-    uint32_t num_blockers = 0;
-    uint32_t blk_ids[PG_MAX_BLOCKERS] = {}, blk_orig[PG_MAX_BLOCKERS] = {};  // BVH-order and original ids
-    float blk[PG_MAX_BLOCKERS][12] = {};
-    float absmax = 0.0f;  // the scene's largest |coordinate|
-    std::vector<GMat> host_mats;
-    // textures (pg_set_textures): nothing is allocated while `textured` is false.  base_mats / base_tclass: the
-    // untextured scene's material records and triangle classes, put back when the textures are turned off
-    bool textured = false;
-    bool scene_rendered = false;  // a render pass ran on the uploaded scene: its textures can no longer change
-    DevBuf tuv, tex, mtex, texels;
-    std::vector<GMat> base_mats;
-    std::vector<uint8_t> base_tclass;
-    std::vector<uint32_t> host_indices;  // the uploaded scene's triangles (their vertices' texcoords)
-    uint32_t num_vertices = 0;
-    float scene_lo[3] = {0, 0, 0}, scene_hi[3] = {0, 0, 0};
-    // delta emitters (pg_set_delta_emitters): nothing is allocated while num_delta is 0.  tri_lo / tri_hi: the
-    // uploaded triangles' box, whose bounding sphere a directional emitter's disk lies on
-    DevBuf delta;
-    uint32_t num_delta = 0, num_area = 0;
-    float tri_lo[3] = {0, 0, 0}, tri_hi[3] = {0, 0, 0};
-    // shard
-    std::vector<uint32_t> local_pixels;
-    DevBuf d_local_pixels;
-    DevBuf d_band_pixels;  // the surface path's order of the same pixels (cameraBands)
-    // path state
-    Lane lanes[PG_MAX_LANES];
-    int nlanes = PG_DEFAULT_LANES;
-    hipEvent_t film_order = nullptr;  // last chunk's film + record commit (keeps them in chunk order)
-    hipEvent_t pass_start = nullptr;
-    uint64_t rec_bound = 0;           // upper bound of the device-side record count
-    EventPair timing;                 // context-stream kernel timing (splat)
-    // film
-    DevBuf film, film_sq;
-    DevBuf aov_albedo, aov_normal;  // per-pixel denoiser feature sums (pg_config.aovs)
-    // reconstruction-filtered film (pg_set_rfilter): nothing is allocated or launched while `filtered` is false
-    bool filtered = false;
-    bool filter_direct = false;  // PG_FILM_FILTER_DIRECT=1, or the padded tile exceeds 64 KiB of LDS
-    bool rendered = false;       // a render pass ran: the filter can no longer change
-    float filter_radius = 0;
-    float filter_values[32] = {};
-    DevBuf film_acc, filter_tab, tile_first, tile_origin;
-    std::vector<uint32_t> h_tile_first;  // local tile k = local pixels [h_tile_first[k], h_tile_first[k + 1])
-    std::vector<uint32_t> h_tile_origin; // (x, y) pairs
-    // records
-    DevBuf records, rec_count;
-    uint64_t rec_capacity = 0;
-    uint64_t rec_host_count = 0;
-    DevBuf ext_records;
-    // sd-tree
-    pgh::SdTree sd;
-    // the device SD-tree lives in one allocation (uploadSd): snodes | meta | qnode {energies, children} |
-    // bchild | bsum | count | frac | jump.  bsum, count and frac are contiguous -- the pg_get_tree_stats
-    // vector -- so the statistics move in one copy (download, all-reduce in place), the host-built
-    // part in one upload, and the jump grid is built on the device from the S-tree.
-    DevBuf sd_blob;
-    struct {
-        uint32_t *snodes = nullptr, *meta = nullptr, *qnode = nullptr, *bchild = nullptr, *jump = nullptr;
-        uint64_t *bsum = nullptr, *count = nullptr, *frac = nullptr;  // frac: pgh::kFracStats u64 per leaf
-    } sdp;
-    int sd_jump_bits = 0;
-    PinnedBuf sd_stage;
-    bool sd_dirty = true;
-    // multi-GPU: RCCL communicator over the job's ranks (pg_comm_init), one per context/device
-    ncclComm_t comm = nullptr;
-    // stats
-    pg_stats stats{};
-    uint64_t culled = 0;  // segments whose hit the tracer culled (pg_get_culled); counted in stats.segments
-    uint64_t probes = 0;  // segments answered by an any-hit probe (pg_get_probes); counted in culled or escaped
-    uint64_t shadow_culled = 0;  // shadow rays resolved against the blocker list; counted in stats.shadow_rays
-};
 
 thread_local std::string g_tls_err;
 
@@ -303,14 +53,6 @@ pg_status fail(Ctx *c, pg_status code, const std::string &msg) {
     else g_tls_err = msg;
     return code;
 }
-
-#define HIPC(c, expr)                                                                                              \
-    do {                                                                                                           \
-        hipError_t e_ = (expr);                                                                                    \
-        if (e_ != hipSuccess)                                                                                      \
-            return fail((c), e_ == hipErrorOutOfMemory ? PG_ERR_OOM : PG_ERR_HIP,                                  \
-                        std::string(#expr) + ": " + hipGetErrorString(e_));                                        \
-    } while (0)
 
 inline float luminance(const float *c) { return c[0] * 0.212671f + c[1] * 0.715160f + c[2] * 0.072169f; }
 
@@ -577,41 +319,6 @@ pg_status downloadSd(Ctx *c) {
     return PG_OK;
 }
 
-EventPair nextEvents(Lane *l, LaunchKind kind) {
-    std::vector<EventPair> &pool = l->ev[l->evcur];
-    std::vector<uint8_t> &kinds = l->evkind[l->evcur];
-    kinds.resize(l->evused[l->evcur] + 1);
-    kinds[l->evused[l->evcur]] = (uint8_t)kind;
-    if (l->evused[l->evcur] == pool.size()) {
-        EventPair e;
-        (void)hipEventCreate(&e.a);
-        (void)hipEventCreate(&e.b);
-        pool.push_back(e);
-    }
-    return pool[l->evused[l->evcur]++];
-}
-
-// ray-sorted trace queues (A/B switch PG_RAY_SORT=1): k_shade writes a ray order key per queued path and
-// a counting sort groups every shard of the next closest-hit queue by direction octant + origin cell
-bool raySortEnabled() {
-    static const bool on = [] {
-        const char *e = std::getenv("PG_RAY_SORT");
-        return e && std::atoi(e) != 0;
-    }();
-    return on;
-}
-constexpr uint32_t kRaySortMinShard = 1024;  // smaller bounces trace unsorted (the sort's launches cost more)
-
-// the tail of a chunk (k_tail): at most this many live paths left -> one launch finishes them all
-// instead of one launch pair + count readback per bounce (PG_TAIL_PATHS overrides; 0 = off)
-uint32_t tailPaths() {
-    static const uint32_t n = [] {
-        const char *e = std::getenv("PG_TAIL_PATHS");
-        return e ? (uint32_t)std::strtoul(e, nullptr, 10) : (uint32_t)1 << 17;  // profiles/r03n_*: 2^17 vs 2^16 +0.3 %
-    }();
-    return n;
-}
-
 // training-vertex slots per path of a pass (only recording passes write training vertices)
 int vertexSlots(const Ctx *c, bool rec) { return rec ? std::max(0, std::min(c->cfg.record_max_vertices, 64)) : 0; }
 
@@ -696,7 +403,40 @@ pg_status ensureRecords(Ctx *c, uint64_t want) {
     return PG_OK;
 }
 
-}  // namespace
+// the camera's XCD-banded shard map (pg_kernels.h pg_banded_shard_count) over PG_CAMERA_BANDS bands of the local
+// pixels (0: the interleaved map): band g goes to XCD group g % 8, so with more than 8 bands each XCD takes
+// every 8th band (the surface path's pixel order d_band_pixels groups them).  Paths are pure functions of
+// (pixel, sample), so films and trees do not depend on it
+uint32_t cameraBands() {
+    const char *e = std::getenv("PG_CAMERA_BANDS");
+    return e && *e ? (uint32_t)std::strtoul(e, nullptr, 10) : 0u;
+}
+
+// k_film_filtered for the chunk k_film has just been launched for (same stream, pixel order and path view)
+void launchFilmFiltered(Ctx *c, hipStream_t s, const GParams &g, const SceneDev &sc, const PathDev &p,
+                        const uint32_t *pixels, uint32_t pb, uint32_t np, uint32_t nl, uint32_t sample_base) {
+    if (!np || !nl) return;
+    FilmFilter f{};
+    f.radius = c->filter_radius;
+    f.scale = 31.0f / c->filter_radius;
+    f.border = (int32_t)std::ceil(c->filter_radius - 0.5f);
+    f.tile = c->cfg.tile_size;
+    f.values = c->filter_tab.as<float>();
+    f.acc = c->film_acc.as<unsigned long long>();
+    f.tile_first = c->tile_first.as<uint32_t>();
+    f.tile_origin = c->tile_origin.as<uint2>();
+    uint32_t tile0 = 0, ntiles = 0;
+    if (!c->filter_direct) {  // the local tiles the chunk's pixel range [pb, pb + np) touches
+        const std::vector<uint32_t> &tf = c->h_tile_first;
+        tile0 = (uint32_t)(std::upper_bound(tf.begin(), tf.end(), pb) - tf.begin()) - 1;
+        ntiles = (uint32_t)(std::upper_bound(tf.begin(), tf.end(), pb + np - 1) - tf.begin()) - tile0;
+    }
+    pg_launch_film_filtered(s, g, sc, p, f, pixels, pb, np, nl, sample_base, tile0, ntiles);
+}
+
+}  // namespace pgh
+
+using namespace pgh;
 
 extern "C" {
 
@@ -919,15 +659,6 @@ pg_status pg_cancel(void *ctx) {
     return PG_OK;
 }
 
-// the camera's XCD-banded shard map (pg_kernels.h pg_banded_shard_count) over PG_CAMERA_BANDS bands of the local
-// pixels (0: the interleaved map): band g goes to XCD group g % 8, so with more than 8 bands each XCD takes
-// every 8th band (the surface path's pixel order d_band_pixels groups them).  Paths are pure functions of
-// (pixel, sample), so films and trees do not depend on it
-uint32_t cameraBands() {
-    const char *e = std::getenv("PG_CAMERA_BANDS");
-    return e && *e ? (uint32_t)std::strtoul(e, nullptr, 10) : 0u;
-}
-
 // ---- reconstruction-filtered film (pg_set_rfilter) ------------------------------------------------------
 // device side of the filter: the table, the local tiles' pixel ranges and origins, and the zeroed sums
 // (needs the scene's film size and tile shard; called by whichever of pg_set_rfilter / pg_upload_scene comes last)
@@ -946,28 +677,6 @@ static pg_status setupFiltered(Ctx *c) {
     c->filter_direct = (e && std::atoi(e) != 0) || pg_film_filter_lds_bytes(c->cfg.tile_size, border) > 65536;
     return PG_OK;
 }
-// k_film_filtered for the chunk k_film has just been launched for (same stream, pixel order and path view)
-static void launchFilmFiltered(Ctx *c, hipStream_t s, const GParams &g, const SceneDev &sc, const PathDev &p,
-                               const uint32_t *pixels, uint32_t pb, uint32_t np, uint32_t nl, uint32_t sample_base) {
-    if (!np || !nl) return;
-    FilmFilter f{};
-    f.radius = c->filter_radius;
-    f.scale = 31.0f / c->filter_radius;
-    f.border = (int32_t)std::ceil(c->filter_radius - 0.5f);
-    f.tile = c->cfg.tile_size;
-    f.values = c->filter_tab.as<float>();
-    f.acc = c->film_acc.as<unsigned long long>();
-    f.tile_first = c->tile_first.as<uint32_t>();
-    f.tile_origin = c->tile_origin.as<uint2>();
-    uint32_t tile0 = 0, ntiles = 0;
-    if (!c->filter_direct) {  // the local tiles the chunk's pixel range [pb, pb + np) touches
-        const std::vector<uint32_t> &tf = c->h_tile_first;
-        tile0 = (uint32_t)(std::upper_bound(tf.begin(), tf.end(), pb) - tf.begin()) - 1;
-        ntiles = (uint32_t)(std::upper_bound(tf.begin(), tf.end(), pb + np - 1) - tf.begin()) - tile0;
-    }
-    pg_launch_film_filtered(s, g, sc, p, f, pixels, pb, np, nl, sample_base, tile0, ntiles);
-}
-
 pg_status pg_rfilter_table(int32_t type, float param, float *radius_out, float *values_out) {
     if (!radius_out || !values_out) return fail(nullptr, PG_ERR_INVALID, "pg_rfilter_table: null argument");
     float radius, stddev = 0.5f;
@@ -1788,956 +1497,6 @@ pg_status pg_upload_scene(void *ctx, const pg_scene_desc *d) {
     if ((s = uploadSd(c))) return s;
     HIPC(c, hipStreamSynchronize(c->stream));
     c->has_scene = true;
-    return PG_OK;
-}
-
-// The volumetric path as a wavefront (pg_volpath.hip k_vcam / k_vflight / k_vvertex / k_vtail) or as the
-// persistent megakernel k_volpath (PG_VOL_WAVEFRONT=0): the same per-path arithmetic and random
-// streams, so the same films and trees
-// (read per chunk, so tests can compare both in one process)
-bool volWavefront() {
-    const char *e = std::getenv("PG_VOL_WAVEFRONT");
-    return e && *e ? std::atoi(e) != 0 : true;
-}
-// the interactions' transmittance walks (NEE shadow walks, emitter walks through media) as a stage of their
-// own (k_vnee, after each k_vvertex; PG_VOL_NEE_STAGE=1) or inline at the end of each k_vvertex interaction
-// (default): both give the same films and trees (the walks draw from their own sub-streams either way).  The
-// stage takes the walks out of k_vvertex (medium interactions at 3 waves/SIMD, 166 VGPRs, no scratch) but the
-// walks then run 45 % slower on their own: C5 328.8 / 326.4 Mpaths/s as a stage, 334.7 / 335.6 with the stage
-// overlapping the next iteration's flights, 373.7 / 373.9 inline on one box (profiles/r05c_vol_nee_stage/)
-bool volNeeStage() {
-    const char *e = std::getenv("PG_VOL_NEE_STAGE");
-    return e && *e ? std::atoi(e) != 0 : false;
-}
-// VolLane path state: VolWave's 14 float4 per slot (7 path columns, 6 deferred-walk columns and their flags /
-// key / sample column; the first 7 when the walks run inline); its queues (pg_volpath.hip)
-constexpr int kVolStateF4 = 14, kVolStateF4Inline = 7, kVolQueues = 8;
-// k_vnee of iteration i on the lane's second stream, concurrent with iteration i + 1's k_vflight (which reads
-// no state the walks write); k_vvertex of i + 1 waits for it.  PG_VOL_NEE_OVERLAP=0: on the lane's stream
-bool volNeeOverlap() {
-    const char *e = std::getenv("PG_VOL_NEE_OVERLAP");
-    return e && *e ? std::atoi(e) != 0 : true;
-}
-// below this many live paths a chunk's remaining paths finish in one k_vtail launch (PG_VOL_TAIL_PATHS): 2^17
-// with three lanes (C5 398.7 / 399.4 against 396.6 / 397.5 at 2^18, profiles/r04al_vol_tail/)
-uint32_t volTailPaths() {
-    const char *e = std::getenv("PG_VOL_TAIL_PATHS");
-    return e && *e ? (uint32_t)std::strtoul(e, nullptr, 10) : (uint32_t)1 << 17;
-}
-
-
-// chunks of a volumetric pass: np pixels from pb, nl sample layers from sample_base
-struct VChunk {
-    uint32_t pb, np, nl, sample_base;
-};
-// flight queues sorted by the 16^3 cell of the flight's start before k_vflight, for shards of at least this
-// many flights (PG_VOL_SORT; 0 = off, the default since round 5).  Round 4: C5 351.5 / 350.0 against
-// 346.3 / 345.7 Mpaths/s unsorted (profiles/r04s_vol_sort/, r04t_vol_ab/).  With round 5's 3-wave interaction
-// launches the sort no longer pays: 442.9 / 442.5 sorted (4096) against 445.0 / 445.8 unsorted, k_vflight
-// 45.3 against 48.9 ms per calibration pass but k_vvertex 136.4 against 133.8 (its state reads no longer
-// scattered) plus the sort kernels (profiles/r05t_vol_tune/)
-uint32_t volSortMin() {
-    const char *e = std::getenv("PG_VOL_SORT");
-    return e && *e ? (uint32_t)std::strtoul(e, nullptr, 10) : 0u;
-}
-// volumetric wavefront lanes in flight: pg_config.path_lanes (default 3, as for the path integrator; C5 at
-// the round-4 kernels: 393.7 / 397.0 / 389.7 Mpaths/s with 2 / 3 / 4 lanes, profiles/r04aj_vol_lanes/);
-// PG_VOL_LANES overrides (A/B)
-int volLanes(const Ctx *c) {
-    const char *e = std::getenv("PG_VOL_LANES");
-    const int n = e && *e ? std::atoi(e) : c->nlanes;
-    return std::max(1, std::min(PG_MAX_LANES, n));
-}
-
-// The chunks of one pass through the wavefront: per chunk the camera rays, then per iteration the
-// free flights and the interactions, until at most volTailPaths() paths live; the tail finishes them.
-// The host reads a chunk's queue counters once per iteration (grid sizes; the kernels read the counts)
-// and advances whichever lane's counters have landed, so one chunk's readback and sparse last
-// iterations overlap another's full ones.  Films (and record commits) run in chunk order, so every
-// pixel's float sums are those of one lane.  Recording passes use two lanes (each with its own region of
-// training vertices), per-stage timing one.
-pg_status volWavefrontPass(Ctx *c, const GParams &g, const SceneDev &sc, const VolDev &v, const SDDev &sd,
-                           const PathDev &pv, const std::vector<VChunk> &chunks, uint32_t want, int maxV,
-                           uint32_t vtxLanes, std::vector<EventPair> &evs) {
-    const bool evt = c->cfg.kernel_timing != 0;
-    const int nl = evt ? 1 : std::min<int>(g.record ? (int)vtxLanes : volLanes(c), (int)chunks.size());
-    // training vertices of lane li (recording passes): region li of vtxLanes, want items each
-    auto laneVtx = [&](const VolLane &l) -> float4 * {
-        return v.vtx ? v.vtx + (size_t)(&l - c->vlanes) * want * (size_t)maxV * PG_VTX_F4 : nullptr;
-    };
-    const size_t cbytes = (size_t)PG_QSHARDS * 4 * kVolQueues;
-    const bool neeStage = volNeeStage(), neeOverlap = neeStage && volNeeOverlap() && !evt;
-    auto joinNee = [&](VolLane &l) -> pg_status {  // the lane's stream waits for its pending walks
-        if (l.npending) {
-            HIPC(c, hipStreamWaitEvent(l.stream, l.ndone, 0));
-            l.npending = false;
-        }
-        return PG_OK;
-    };
-    const uint32_t sortMin = volSortMin();
-    HIPC(c, hipEventRecord(c->pass_start, c->stream));  // lanes start after the context stream's work
-    for (int li = 0; li < nl; ++li) {
-        VolLane &l = c->vlanes[li];
-        if (!l.stream) {
-            HIPC(c, hipStreamCreateWithFlags(&l.stream, hipStreamNonBlocking));
-            HIPC(c, hipEventCreateWithFlags(&l.ready, hipEventDisableTiming));
-        }
-        // the second stream only when the overlapped k_vnee stage runs: HIP maps a process's streams onto
-        // GPU_MAX_HW_QUEUES (4) hardware queues, and with one more stream per lane two lanes shared a queue
-        // and serialized (C5 380 against 400 Mpaths/s, profiles/r05h_vol_streams/)
-        if (neeOverlap && !l.nstream) {
-            HIPC(c, hipStreamCreateWithFlags(&l.nstream, hipStreamNonBlocking));
-            HIPC(c, hipEventCreateWithFlags(&l.vdone, hipEventDisableTiming));
-            HIPC(c, hipEventCreateWithFlags(&l.ndone, hipEventDisableTiming));
-        }
-        l.npending = false;
-        const int f4 = neeStage ? kVolStateF4 : kVolStateF4Inline;  // the stage's records only when it runs
-        if (l.cap < want || l.stateF4 != f4) {
-            const uint32_t lc = std::max(want, l.cap);
-            HIPC(c, l.state.alloc((size_t)lc * 16 * f4));
-            l.stateF4 = f4;
-            HIPC(c, l.items.alloc((size_t)pg_queue_stride(lc) * PG_QSHARDS * 4 * kVolQueues));
-            HIPC(c, l.rad.alloc((size_t)lc * 16));
-            l.cap = lc;
-        }
-        HIPC(c, l.counts.alloc(cbytes));
-        HIPC(c, l.host.reserve(cbytes));
-        if (sortMin) {
-            const size_t qstride = (size_t)pg_queue_stride(l.cap) * PG_QSHARDS;
-            HIPC(c, l.keys.alloc(qstride * 2 * 2));
-            HIPC(c, l.sorted.alloc(qstride * 4));
-            HIPC(c, l.hist.alloc((size_t)PG_QSHARDS * PG_RAY_SORT_BINS * 4));
-        }
-        if (!l.ovf.p) HIPC(c, l.ovf.alloc(pg_stack_overflow_words(0) * 4));
-        HIPC(c, hipStreamWaitEvent(l.stream, c->pass_start, 0));
-        l.active = l.waved = false;
-    }
-    HIPC(c, hipEventRecord(c->film_order, c->stream));
-    const uint32_t tail = volTailPaths();
-    uint32_t next = 0, filmNext = 0;
-    auto views = [&](VolLane &l, VolDev &lv, VolWave &w, Queue *q) {  // q: kVolQueues queues
-        lv = v;
-        lv.rad = l.rad.as<float4>();
-        lv.stack_ovf = l.ovf.as<uint32_t>();
-        lv.vtx = laneVtx(l);
-        float4 *st = l.state.as<float4>();
-        const size_t cap = l.cap;
-        w = VolWave{st, st + cap, reinterpret_cast<uint4 *>(st + 2 * cap), st + 3 * cap, st + 4 * cap,
-                    reinterpret_cast<uint4 *>(st + 5 * cap), st + 6 * cap};
-        if (l.stateF4 == kVolStateF4) {  // the k_vnee stage's deferred-walk records
-            w.n0 = st + 7 * cap;
-            w.n1 = st + 8 * cap;
-            w.n2 = st + 9 * cap;
-            w.h0 = st + 10 * cap;
-            w.h1 = st + 11 * cap;
-            w.h2 = st + 12 * cap;
-            w.nflags = reinterpret_cast<uint4 *>(st + 13 * cap);
-        }
-        // queues 0/1: flight of even / odd iterations, 2/3: surface, 4: medium vertices, 5/6: delta surface,
-        // 7: deferred transmittance walks (k_vnee)
-        const size_t qstride = (size_t)pg_queue_stride(l.cap) * PG_QSHARDS;
-        const uint32_t stride = pg_queue_stride(l.np * l.nl);
-        for (int k = 0; k < kVolQueues; ++k)
-            q[k] = Queue{l.items.as<uint32_t>() + k * qstride, l.counts.as<uint32_t>() + k * PG_QSHARDS, stride};
-        if (sortMin)
-            for (int k = 0; k < 2; ++k) q[k].keys = l.keys.as<uint16_t>() + k * qstride;
-    };
-    auto readback = [&](VolLane &l) -> pg_status {
-        HIPC(c, hipMemcpyAsync(l.host.p, l.counts.p, cbytes, hipMemcpyDeviceToHost, l.stream));
-        HIPC(c, hipEventRecord(l.ready, l.stream));
-        return PG_OK;
-    };
-    auto start = [&](VolLane &l) -> pg_status {
-        if (next >= chunks.size()) {
-            l.active = false;
-            return PG_OK;
-        }
-        const VChunk &ch = chunks[next];
-        l.chunk = next++;
-        l.pb = ch.pb, l.np = ch.np, l.nl = ch.nl, l.sample_base = ch.sample_base;
-        l.it = 0;
-        l.active = true;
-        l.waved = false;
-        HIPC(c, hipEventCreate(&l.span.a));
-        HIPC(c, hipEventCreate(&l.span.b));
-        HIPC(c, hipEventRecord(l.span.a, l.stream));
-        VolDev lv;
-        VolWave w;
-        Queue q[kVolQueues];
-        views(l, lv, w, q);
-        HIPC(c, hipMemsetAsync(l.counts.p, 0, cbytes, l.stream));
-        pg_launch_vol_camera(l.stream, g, sc, lv, w, c->d_local_pixels.as<uint32_t>(), l.pb, l.np, l.nl, l.sample_base,
-                             q[0], q[2], q[5]);
-        HIPC(c, hipGetLastError());
-        return readback(l);
-    };
-    // record commit + film of a chunk whose paths are done (its turn in chunk order), then its next chunk
-    auto finish = [&](VolLane &l) -> pg_status {
-        HIPC(c, hipStreamWaitEvent(l.stream, c->film_order, 0));
-        PathDev lp = pv;
-        lp.rad = l.rad.as<float4>();
-        lp.vtx = laneVtx(l);
-        if (g.record) {
-            const uint64_t items = (uint64_t)l.np * l.nl, add = items * (uint64_t)maxV;
-            if (c->rec_bound + add > c->rec_capacity) {
-                unsigned long long rc = 0;
-                HIPC(c, hipStreamSynchronize(l.stream));
-                HIPC(c, hipMemcpy(&rc, c->rec_count.p, 8, hipMemcpyDeviceToHost));
-                c->stats.records += rc - c->rec_host_count;
-                c->rec_host_count = c->rec_bound = rc;
-                pg_status st;
-                if ((st = ensureRecords(c, rc + add))) return st;
-            }
-            c->rec_bound += add;
-            pg_launch_commit(l.stream, lp, (uint32_t)items, maxV, c->records.as<pg_record>(),
-                             c->rec_count.as<unsigned long long>(), c->rec_capacity, 0);
-        }
-        pg_launch_film(l.stream, g, sc, lp, c->d_local_pixels.as<uint32_t>(), l.pb, l.np, l.nl, c->film.as<float4>(),
-                       c->film_sq.as<float4>());
-        if (c->filtered)
-            launchFilmFiltered(c, l.stream, g, sc, lp, c->d_local_pixels.as<uint32_t>(), l.pb, l.np, l.nl, l.sample_base);
-        HIPC(c, hipGetLastError());
-        HIPC(c, hipEventRecord(c->film_order, l.stream));
-        HIPC(c, hipEventRecord(l.span.b, l.stream));
-        evs.push_back(l.span);
-        l.span = EventPair{};
-        c->stats.paths += (uint64_t)l.np * l.nl;
-        return start(l);
-    };
-    // one iteration of lane l (its counters are on the host)
-    auto advance = [&](VolLane &l) -> pg_status {
-        if (c->cancel.load()) return fail(c, PG_ERR_CANCELLED, "cancelled");
-        const uint32_t *hc = reinterpret_cast<const uint32_t *>(l.host.p);
-        auto maxShard = [&](int k) {
-            uint32_t m = 0, t = 0;
-            for (int i = 0; i < PG_QSHARDS; ++i) {
-                m = std::max(m, hc[k * PG_QSHARDS + i]);
-                t += hc[k * PG_QSHARDS + i];
-            }
-            return std::make_pair(m, t);
-        };
-        VolDev lv;
-        VolWave w;
-        Queue q[kVolQueues];
-        views(l, lv, w, q);
-        const int cur = l.it & 1, nxt = cur ^ 1;
-        const auto f = maxShard(cur), su = maxShard(2 + cur), sdl = maxShard(5 + cur);
-        if (f.second + su.second + sdl.second <= tail) {
-            if (pg_status js = joinNee(l)) return js;
-            if (f.second + su.second + sdl.second) {
-                pg_launch_vol_tail(l.stream, g, sc, lv, sd, w, q[cur], f.first, q[2 + cur], su.first, q[5 + cur],
-                                   sdl.first);
-                HIPC(c, hipGetLastError());
-            }
-            l.waved = true;
-            // finish this chunk and every waiting one whose turn comes after it
-            for (bool progress = true; progress;) {
-                progress = false;
-                for (int k = 0; k < nl; ++k) {
-                    VolLane &o = c->vlanes[k];
-                    if (o.active && o.waved && o.chunk == filmNext) {
-                        ++filmNext;
-                        pg_status st = finish(o);
-                        if (st) return st;
-                        progress = true;
-                    }
-                }
-            }
-            return PG_OK;
-        }
-        // the next iteration's output queues and the medium queue start empty
-        HIPC(c, hipMemsetAsync(q[nxt].counts, 0, PG_QSHARDS * 4, l.stream));
-        HIPC(c, hipMemsetAsync(q[2 + nxt].counts, 0, PG_QSHARDS * 4, l.stream));
-        HIPC(c, hipMemsetAsync(q[4].counts, 0, PG_QSHARDS * 4, l.stream));
-        HIPC(c, hipMemsetAsync(q[5 + nxt].counts, 0, PG_QSHARDS * 4, l.stream));
-        // per-stage device time (pg_config.kernel_timing, one lane): events around each launch
-        if (evt && !c->vw_ev[0])
-            for (hipEvent_t &e : c->vw_ev) HIPC(c, hipEventCreate(&e));
-        Queue fq = q[cur];
-        if (sortMin && f.first >= sortMin) {  // the flights in cell order (same shards and counts)
-            pg_launch_ray_sort(l.stream, fq, f.first, l.sorted.as<uint32_t>(), l.hist.as<uint32_t>(), PG_VOL_SORT_BINS);
-            fq.items = l.sorted.as<uint32_t>();
-        }
-        if (evt) HIPC(c, hipEventRecord(c->vw_ev[0], l.stream));
-        pg_launch_vol_flight(l.stream, g, sc, lv, sd, w, fq, f.first, q[4], q[2 + cur], q[5 + cur]);
-        if (evt) HIPC(c, hipEventRecord(c->vw_ev[1], l.stream));
-        // shard bounds without a readback: a medium vertex came from a flight; a surface vertex from a
-        // flight or from the previous iteration's interactions; no shard exceeds the queue stride
-        const uint32_t mm = f.first, ms = std::min(q[0].stride, f.first + su.first + sdl.first);
-        // the previous iteration's walks write L: done before this iteration's interactions read it
-        if (pg_status js = joinNee(l)) return js;
-        if (neeStage) HIPC(c, hipMemsetAsync(q[7].counts, 0, PG_QSHARDS * 4, l.stream));
-        const int vk = pg_launch_vol_vertex(l.stream, g, sc, lv, sd, w, q[4], mm, q[2 + cur], ms, q[5 + cur], ms,
-                                            q[nxt], q[2 + nxt], q[5 + nxt], neeStage ? &q[7] : nullptr);
-        if (evt) HIPC(c, hipEventRecord(c->vw_ev[2], l.stream));
-        // the deferred walks: at most one entry per path live in this iteration (<= ms per shard)
-        if (neeOverlap) {
-            HIPC(c, hipEventRecord(l.vdone, l.stream));
-            HIPC(c, hipStreamWaitEvent(l.nstream, l.vdone, 0));
-            pg_launch_vol_nee(l.nstream, g, sc, lv, w, q[7], ms);
-            HIPC(c, hipEventRecord(l.ndone, l.nstream));
-            l.npending = true;
-        } else if (neeStage) {
-            pg_launch_vol_nee(l.stream, g, sc, lv, w, q[7], ms);
-        }
-        if (evt) {
-            HIPC(c, hipEventRecord(c->vw_ev[3], l.stream));
-            HIPC(c, hipEventSynchronize(c->vw_ev[3]));
-            float a = 0, b = 0, e = 0;
-            if (f.first) {
-                HIPC(c, hipEventElapsedTime(&a, c->vw_ev[0], c->vw_ev[1]));
-                c->stats.vol_flight_ms += a;
-                c->stats.vol_flight_launches++;
-            }
-            HIPC(c, hipEventElapsedTime(&b, c->vw_ev[1], c->vw_ev[2]));
-            c->stats.vol_vertex_ms += b;
-            c->stats.vol_vertex_launches += vk;  // kernels, not stages: the medium and surface launches
-            if (neeStage) {
-                HIPC(c, hipEventElapsedTime(&e, c->vw_ev[2], c->vw_ev[3]));
-                c->stats.vol_nee_ms += e;
-                c->stats.vol_nee_launches++;
-            }
-        }
-        HIPC(c, hipGetLastError());
-        ++l.it;
-        return readback(l);
-    };
-    pg_status s;
-    for (int li = 0; li < nl; ++li)
-        if ((s = start(c->vlanes[li]))) return s;
-    // advance whichever lane has its counters first
-    for (uint32_t rr = 0;; ++rr) {
-        int active = 0, picked = -1;
-        for (int k = 0; k < nl; ++k) {
-            VolLane &l = c->vlanes[(rr + k) % nl];
-            if (!l.active) continue;
-            ++active;
-            if (l.waved) continue;  // waiting for an earlier chunk's film
-            const hipError_t qr = hipEventQuery(l.ready);
-            if (qr == hipSuccess) {
-                picked = (int)((rr + k) % nl);
-                break;
-            }
-            if (qr != hipErrorNotReady) HIPC(c, qr);
-        }
-        if (!active) break;
-        if (picked >= 0 && (s = advance(c->vlanes[picked]))) return s;
-    }
-    for (int li = 0; li < nl; ++li) HIPC(c, hipStreamSynchronize(c->vlanes[li].stream));
-    return PG_OK;
-}
-
-// progressive_volpath: chunks of (pixel, sample) items through the wavefront or k_volpath, films in chunk order
-pg_status renderVolpath(Ctx *c, uint32_t spp, uint32_t sample_offset, bool rec) {
-    const uint32_t npix = (uint32_t)c->local_pixels.size();
-    // 2^25 items per launch: fewer persistent-kernel tails (C5 guided: 177.8 -> 189.8 Mpaths/s
-    // against 2^22, profiles/r01h_c5_*.log); 50 GB of training vertices when guided
-    const uint32_t cap = c->cfg.max_paths_in_flight ? c->cfg.max_paths_in_flight : (1u << 25);
-    const uint64_t total = (uint64_t)npix * spp;
-    uint32_t want = (uint32_t)std::min<uint64_t>(total, cap);
-    const bool wave = volWavefront();  // the wavefront's lanes hold their own radiance and overflow rings
-    const int maxV = std::min(std::max(c->cfg.record_max_vertices, 0), 64);
-    // a recording pass through the wavefront runs as (at least) two chunks on two lanes, each lane with
-    // its own region of training vertices (indexed by item within the chunk): the same vertex memory as
-    // one chunk of the whole pass
-    const char *rl = std::getenv("PG_VOL_REC_LANES");  // 1: one lane (A/B)
-    const uint32_t vtxLanes = (wave && rec && maxV > 0 && !c->cfg.kernel_timing && volLanes(c) >= 2 && total > 1 &&
-                               !(rl && std::atoi(rl) == 1)) ? 2u : 1u;
-    if (vtxLanes == 2) want = (uint32_t)std::min<uint64_t>(want, (total + 1) / 2);
-    if (!wave && c->vol_cap < want) {
-        HIPC(c, c->vol_rad.alloc((size_t)want * 16));
-        c->vol_cap = want;
-    }
-    if (rec && maxV > 0 && c->vol_vtx_cap < (uint64_t)want * maxV * vtxLanes) {
-        HIPC(c, c->vol_vtx.alloc((size_t)want * maxV * vtxLanes * 16 * PG_VTX_F4));
-        c->vol_vtx_cap = (uint64_t)want * maxV * vtxLanes;
-    }
-    if (!wave && !c->vol_ovf.p) HIPC(c, c->vol_ovf.alloc(pg_stack_overflow_words(0) * 4));
-    HIPC(c, c->vol_work.alloc(128));  // work counter, then 7 u64 statistics from byte 16
-    HIPC(c, hipMemsetAsync(c->vol_work.p, 0, 128, c->stream));
-    GParams g = c->g;
-    g.max_depth = c->cfg.max_depth;
-    g.rr_depth = c->cfg.rr_depth;
-    g.use_nee = c->cfg.use_nee;
-    g.hide_emitters = c->cfg.hide_emitters;
-    g.strict_normals = c->cfg.strict_normals;
-    g.max_component_value = c->cfg.max_component_value;
-    g.seed = c->cfg.seed;
-    g.depth_cap = deviceDepthCap(c->cfg);
-    g.guiding = c->cfg.guiding;
-    g.bsdf_fraction = c->cfg.bsdf_sampling_fraction;
-    g.fraction_bound = c->cfg.bsdf_fraction_bound;
-    g.exact_mis = c->cfg.volpath_exact_mis;
-    g.record = rec && maxV > 0;
-    g.max_vertices = maxV;
-    const SceneDev sc = sceneView(c);
-    const SDDev sd = sdView(c);
-    VolDev v{};
-    v.grid = c->cfg.volume_majorant == PG_MAJORANT_GRID ? 1 : 0;
-    v.media = c->media.as<GMedium>();
-    v.tmed = c->tmed.as<uint32_t>();
-    v.tcheap = c->tcheap.as<uint8_t>();
-    {  // the surface launches specialised to diffuse / null materials (read per pass: tests A/B it in-process)
-        const char *e = std::getenv("PG_VOL_MODELS");
-        v.models = c->diffuse_null && !(e && *e && std::atoi(e) == 0) ? 1u : 0u;
-    }
-    v.cam_medium = c->cam_medium;
-    v.num_media = c->num_media;
-    v.rad = c->vol_rad.as<float4>();
-    v.next = c->vol_work.as<uint32_t>();
-    v.stats = (unsigned long long *)(c->vol_work.as<uint8_t>() + 16);
-    v.stack_ovf = c->vol_ovf.as<uint32_t>();
-    v.vtx = g.record ? c->vol_vtx.as<float4>() : nullptr;
-    v.vtx_P = want;
-    v.dist_beta = c->cfg.distance_guiding;
-    {  // refill threshold of the persistent volumetric kernel: C5 198 / 212 / 227 / 243 / 248 / 247 / 242 /
-       // 211 Mpaths/s at 1 / 8 / 16 / 32 / 40 / 48 / 56 / 64 idle lanes (profiles/r03p_vol_refill/);
-       // PG_VOL_REFILL overrides (A/B)
-        const char *e = std::getenv("PG_VOL_REFILL");
-        v.refill_min = e ? (uint32_t)std::max(1, std::min(64, std::atoi(e))) : 40u;
-    }
-    PathDev pv{};
-    pv.rad = v.rad;
-    pv.vtx = v.vtx;
-    pv.P = want;
-    pv.vtxP = want;
-    pv.vst = nullptr;  // k_commit reads the vertex count from rad[item].w
-    const uint32_t layersPer = std::max<uint32_t>(1, want / npix), pixPer = std::min(npix, want);
-    std::vector<VChunk> chunks;
-    for (uint32_t layer = 0; layer < spp;) {
-        const uint32_t nl = npix > want ? 1 : std::min(layersPer, spp - layer);
-        for (uint32_t pb = 0; pb < npix; pb += pixPer)
-            chunks.push_back(VChunk{pb, std::min(pixPer, npix - pb), nl, sample_offset + layer});
-        layer += nl;
-    }
-    std::vector<EventPair> evs;
-    struct EventsGuard {  // the chunk spans, on every exit (an error or cancellation returns early)
-        std::vector<EventPair> &v;
-        ~EventsGuard() {
-            for (EventPair &e : v) {
-                (void)hipEventDestroy(e.a);
-                (void)hipEventDestroy(e.b);
-            }
-        }
-    } evsGuard{evs};
-    if (wave) {
-        pg_status ws = volWavefrontPass(c, g, sc, v, sd, pv, chunks, want, maxV, vtxLanes, evs);
-        if (ws) return ws;
-    }
-    for (size_t ci = 0; !wave && ci < chunks.size(); ++ci) {  // the persistent megakernel
-        if (c->cancel.load()) return fail(c, PG_ERR_CANCELLED, "cancelled");
-        const uint32_t pb = chunks[ci].pb, np = chunks[ci].np, nl = chunks[ci].nl;
-        EventPair e;
-        HIPC(c, hipEventCreate(&e.a));
-        HIPC(c, hipEventCreate(&e.b));
-        evs.push_back(e);
-        HIPC(c, hipEventRecord(e.a, c->stream));
-        pg_launch_volpath(c->stream, g, sc, v, sd, c->d_local_pixels.as<uint32_t>(), pb, np, nl, chunks[ci].sample_base);
-        HIPC(c, hipEventRecord(e.b, c->stream));
-        if (g.record) {
-            const uint64_t items = (uint64_t)np * nl, add = items * (uint64_t)maxV;
-            if (c->rec_bound + add > c->rec_capacity) {
-                unsigned long long rc = 0;
-                HIPC(c, hipStreamSynchronize(c->stream));
-                HIPC(c, hipMemcpy(&rc, c->rec_count.p, 8, hipMemcpyDeviceToHost));
-                c->stats.records += rc - c->rec_host_count;
-                c->rec_host_count = c->rec_bound = rc;
-                pg_status st;
-                if ((st = ensureRecords(c, rc + add))) return st;
-            }
-            c->rec_bound += add;
-            pg_launch_commit(c->stream, pv, (uint32_t)items, maxV, c->records.as<pg_record>(),
-                             c->rec_count.as<unsigned long long>(), c->rec_capacity, 0);
-        }
-        pg_launch_film(c->stream, g, sc, pv, c->d_local_pixels.as<uint32_t>(), pb, np, nl, c->film.as<float4>(),
-                       c->film_sq.as<float4>());
-        if (c->filtered)
-            launchFilmFiltered(c, c->stream, g, sc, pv, c->d_local_pixels.as<uint32_t>(), pb, np, nl, chunks[ci].sample_base);
-        HIPC(c, hipGetLastError());
-        c->stats.paths += (uint64_t)np * nl;
-    }
-    HIPC(c, hipStreamSynchronize(c->stream));
-    unsigned long long st[9];
-    HIPC(c, hipMemcpy(st, c->vol_work.as<uint8_t>() + 16, 72, hipMemcpyDeviceToHost));
-    c->stats.vol_nee_walks += st[7];
-    c->stats.vol_nee_lookups += st[8];
-    c->stats.vol_flights += st[3];
-    c->stats.vol_flight_lookups += st[4];
-    c->stats.vol_vertices += st[5];
-    c->stats.vol_vertex_lookups += st[6];
-    c->stats.segments += st[0];
-    c->stats.shadow_rays += st[1];
-    c->stats.density_lookups += st[2];
-    if (g.record) {
-        unsigned long long rc = 0;
-        HIPC(c, hipMemcpy(&rc, c->rec_count.p, 8, hipMemcpyDeviceToHost));
-        c->stats.records += rc - c->rec_host_count;
-        c->rec_host_count = c->rec_bound = rc;
-    }
-    for (EventPair &e : evs) {
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, e.a, e.b);
-        c->stats.volume_ms += ms;
-        c->stats.volume_launches++;
-    }
-    return PG_OK;
-}
-
-// Every exit of a pass that did not complete (cancellation, a HIP error): the lane streams are created
-// non-blocking, so nothing queued later on c->stream (pg_read_film, pg_reset_film) orders after them.
-// Wait for them, so that no lane kernel still writes the film or the records once pg_render_pass has
-// returned, and release the chunk span events a volumetric lane had not handed over yet.
-static void drainLanes(Ctx *c) {
-    for (int li = 0; li < c->nlanes; ++li)
-        if (c->lanes[li].stream) (void)hipStreamSynchronize(c->lanes[li].stream);
-    for (VolLane &l : c->vlanes) {
-        if (l.nstream) (void)hipStreamSynchronize(l.nstream);
-        if (l.stream) (void)hipStreamSynchronize(l.stream);
-        l.npending = false;
-        if (l.span.a) (void)hipEventDestroy(l.span.a);
-        if (l.span.b) (void)hipEventDestroy(l.span.b);
-        l.span = EventPair{};
-        l.active = l.waved = false;
-    }
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-}
-
-static pg_status renderPass(Ctx *c, uint32_t spp, uint32_t sample_offset, int32_t record);
-
-pg_status pg_render_pass(void *ctx, uint32_t spp, uint32_t sample_offset, int32_t record) {
-    Ctx *c = (Ctx *)ctx;
-    if (!c) return fail(nullptr, PG_ERR_INVALID, "pg_render_pass: null context");
-    if (!c->has_scene) return fail(c, PG_ERR_STATE, "pg_render_pass: no scene uploaded");
-    if (c->cancel.load()) return fail(c, PG_ERR_CANCELLED, "cancelled");
-    HIPC(c, hipSetDevice(c->cfg.device));
-    c->rendered = true;
-    const pg_status s = renderPass(c, spp, sample_offset, record);
-    if (s) drainLanes(c);
-    return s;
-}
-
-static pg_status renderPass(Ctx *c, uint32_t spp, uint32_t sample_offset, int32_t record) {
-    const uint32_t npix = (uint32_t)c->local_pixels.size();
-    c->scene_rendered = true;
-    if (npix == 0 || spp == 0) return PG_OK;
-    if (c->cfg.integrator == PG_INTEGRATOR_VOLPATH) return renderVolpath(c, spp, sample_offset, record && c->cfg.guiding);
-    const bool rec = record && c->cfg.guiding;
-    // 2^25 paths per chunk by default: bigger chunks mean fewer sparse tail bounces (each costs a
-    // class-count readback) per path.  C3 with 3 lanes: 2^22 491, 2^23 552, 2^24 569, 2^25 587
-    // Mpaths/s (DESIGN.md "Lanes"; round 2: 2^26 / 2^27 within noise, profiles/r02zq_chunk_ab).  Round 6, with
-    // the faster kernels, C3's final render (943.7 M paths, 3 lanes) by chunk count: 30 (2^25) 633-644, 15
-    // (2^26) 646-650, 12 655-660, 9 (2^27) 637-648 Mpaths/s (profiles/r06_chunk/, r06_chunk2/).  So a pass of at
-    // least 3 x lanes x 2^26 paths is cut into four rounds of lanes (whole sample layers, at most 2^27 paths a
-    // chunk); smaller passes (training, an N-GPU shard) keep 2^25 so every lane still gets several chunks.
-    // A non-recording lane holds ~6.1 GB per 2^25 paths; recording lanes add 32 training vertices per path.
-    const uint64_t total = (uint64_t)npix * spp;
-    uint32_t cap = c->cfg.max_paths_in_flight ? c->cfg.max_paths_in_flight : (1u << 25);
-    if (!c->cfg.max_paths_in_flight && total >= 3ull * (uint64_t)c->nlanes * (1ull << 26)) {
-        const uint32_t rounds = 4u * (uint32_t)c->nlanes;
-        cap = (uint32_t)std::min<uint64_t>((uint64_t)((spp + rounds - 1) / rounds) * npix, 1ull << 27);
-    }
-    if (!c->cfg.max_paths_in_flight) {
-        // ... but at most 70 % of the device memory this context can use for path state (free memory
-        // plus what its lanes already hold), e.g. when several contexts or ranks share one GPU
-        size_t freeB = 0, totalB = 0;
-        if (hipMemGetInfo(&freeB, &totalB) == hipSuccess && freeB > 0) {
-            size_t held = 0;
-            for (int li = 0; li < c->nlanes; ++li) {
-                const Lane &l = c->lanes[li];
-                for (const DevBuf *b : {&l.ray, &l.hit, &l.rad, &l.vst,
-                                        &l.sh_d, &l.sh_c, &l.vtx, &l.q0, &l.q1, &l.qs, &l.qp, &l.class_q, &l.aov})
-                    held += b->bytes;
-            }
-            const int vs = vertexSlots(c, rec);
-            const double perPath = 8.0 * 16 + (4 + PG_NUM_CLASSES) * 4.0 + vs * 16.0 * PG_VTX_F4 + (c->cfg.aovs ? 16.0 : 0.0);
-            const double fit = 0.7 * (double)(freeB + held) / (perPath * c->nlanes);
-            if (fit < (double)cap) cap = std::max<uint32_t>(1u << 20, (uint32_t)fit & ~4095u);
-        }
-    }
-    uint32_t want;
-    pg_status s;
-    for (;;) {
-        // chunk count rounded up to whole rounds of lanes, so that the last round keeps every lane busy
-        // (a rank of an N-GPU job may get only a few chunks of the final render); small passes split
-        // into one chunk per lane
-        uint64_t chunks = std::max<uint64_t>(1, (total + cap - 1) / cap);
-        chunks = (chunks + c->nlanes - 1) / c->nlanes * c->nlanes;
-        // a small pass (early training iterations, a rank's shard of them) runs as ONE chunk: three
-        // lanes would each pay the whole bounce tail of launches and count readbacks for a third of
-        // the paths.  Per-pixel sums keep their layer order either way.
-        if (total <= smallPass()) chunks = 1;
-        if ((uint64_t)npix * chunks <= total) {  // whole sample layers per chunk
-            const uint64_t layers = (spp + chunks - 1) / chunks;
-            want = (uint32_t)std::min<uint64_t>(layers * npix, cap);
-        } else {
-            want = (uint32_t)std::min<uint64_t>((total + chunks - 1) / chunks, cap);
-        }
-        s = ensurePaths(c, want, rec);
-        if (s != PG_ERR_OOM || cap <= (1u << 20)) break;
-        // out of device memory (e.g. contexts sharing a GPU sized their chunks from the same free
-        // memory): release the lanes and retry with half the chunk size, down to 2^20 paths
-        releasePaths(c);
-        (void)hipGetLastError();
-        cap = std::max<uint32_t>(1u << 20, (cap / 2) & ~4095u);
-    }
-    if (s) return s;
-    GParams g = c->g;
-    g.max_depth = c->cfg.max_depth;
-    g.rr_depth = c->cfg.rr_depth;
-    g.use_nee = c->cfg.use_nee;
-    g.hide_emitters = c->cfg.hide_emitters;
-    g.strict_normals = c->cfg.strict_normals;
-    g.guiding = c->cfg.guiding;
-    g.record = rec ? 1 : 0;
-    g.max_vertices = rec ? std::min(vertexSlots(c, rec), c->lanes[0].vtx_slots) : 0;
-    g.max_component_value = c->cfg.max_component_value;
-    g.bsdf_fraction = c->cfg.bsdf_sampling_fraction;
-    g.fraction_bound = c->cfg.bsdf_fraction_bound;
-    g.glossy_prior = c->cfg.glossy_prior;
-    g.seed = c->cfg.seed;
-    g.depth_cap = deviceDepthCap(c->cfg);
-    SceneDev sc = sceneView(c);
-    // recording passes count the triangles that block shadow rays (pg_layout.h "Shadow blockers")
-    const bool learn = rec && !c->has_env && g.use_nee && !c->blk_stopped && !std::getenv("PG_NO_SHADOW_CULL");
-
-    if (learn) {
-        sc.blk_counts = c->blk_counts.as<uint32_t>();
-        sc.blk_total = sc.blk_counts + c->num_tris;
-    }
-    const SDDev sd = sdView(c);
-    const uint32_t maxBounces = std::min<uint32_t>(g.depth_cap + 2, kMaxBounces);
-    const bool evt = c->cfg.kernel_timing != 0;  // per-launch HIP events (pg_stats trace/shade/shadow_ms)
-    // the fused launches (k_rays: shadow rays + next closest hits; k_shade_all: every material class)
-    // are what a render runs; with kernel_timing they are timed as launched (pg_stats rays_ms /
-    // shade_ms), so a one-lane calibration context measures the shipped kernels
-    const bool fuseRays = !std::getenv("PG_NO_RAYS_FUSION");
-    // PF_DOOMED (pg_layout.h): roulette and depth exits decided one bounce early, doomed non-emitter hits culled
-    // by the tracer; PG_NO_PATH_CULL=1 runs every vertex through the shader as before (same results)
-    g.path_cull = std::getenv("PG_NO_PATH_CULL") ? 0 : 1;
-    // doom probe (pg_layout.h): doomed rays that miss every emitter box get an any-hit probe instead of the closest-hit
-    // walk; PG_NO_DOOM_PROBE=1 (or no path cull) traces them all as before (same results).  Never with an environment
-    // emitter: an escaping doomed ray picks up its radiance.
-    g.doom_probe = (g.path_cull && !c->has_env && !std::getenv("PG_NO_DOOM_PROBE")) ? 1 : 0;
-    const bool bands = cameraBands() > 0;
-    const bool fuseShade = !c->has_env && !std::getenv("PG_NO_SHADE_FUSION");
-    // chunks: whole sample layers over the local pixels when they fit, else pixel ranges
-    const uint32_t layersPer = std::max<uint32_t>(1, want / npix);
-    const uint32_t pixPer = std::min(npix, want);
-    uint32_t nextLayer = 0, nextPix = 0, nextChunk = 0;  // chunk cursor
-    uint32_t filmNext = 0;  // chunk whose film is next: films run in chunk order, so the float sums
-                            // of a pixel do not depend on which lane finishes first
-    // the lanes start after everything already queued on the context stream (film reset, uploads)
-    HIPC(c, hipEventRecord(c->pass_start, c->stream));
-    HIPC(c, hipEventRecord(c->film_order, c->stream));
-    c->rec_bound = c->rec_host_count;
-
-    auto lqueue = [](const Lane &l, uint32_t *items, uint32_t *counts) {
-        return Queue{items, counts, pg_queue_stride(l.P)};
-    };
-    auto classQueues = [&](const Lane &l, uint32_t *cb, Queue *cls) {
-        for (int k = 0; k < PG_CLASS_ROWS; ++k)
-            cls[k] = lqueue(l, k < PG_NUM_CLASSES ? l.class_q.as<uint32_t>() + (size_t)k * PG_QSHARDS * pg_queue_stride(l.P)
-                                                 : nullptr,
-                            cb + kClassCounts + k * PG_QSHARDS);
-    };
-    // trace of bounce l.b (closest hit + material-class partition), then the class counts to the host;
-    // shq, pq: the previous bounce's shadow and probe queues, traced in the same launch (k_rays)
-    auto launchTrace = [&](Lane &l, const Queue *shq, const Queue *pq) -> pg_status {
-        uint32_t *cb = l.counters.as<uint32_t>() + (size_t)kBounceWords * l.b;
-        Queue cls[PG_CLASS_ROWS];
-        classQueues(l, cb, cls);
-        EventPair et{};
-        if (evt) et = nextEvents(&l, shq ? KT_RAYS : KT_TRACE);
-        if (evt) HIPC(c, hipEventRecord(et.a, l.stream));
-        const Queue tq = lqueue(l, l.sorted ? l.qsorted.as<uint32_t>() : (l.b & 1) ? l.q1.as<uint32_t>() : l.q0.as<uint32_t>(),
-                                cb);
-        if (shq) pg_launch_rays(l.stream, g, sc, pathView(&l), tq, l.bound, cls, *shq, l.bound, *pq);
-        else pg_launch_trace(l.stream, g, sc, pathView(&l), tq, l.bound, cls, l.b == 0);
-        if (evt) HIPC(c, hipEventRecord(et.b, l.stream));
-        HIPC(c, hipMemcpyAsync(l.h_counts + (size_t)kBounceWords * l.b + kClassCounts, cb + kClassCounts,
-                               PG_CLASS_ROWS * PG_QSHARDS * 4, hipMemcpyDeviceToHost, l.stream));
-        HIPC(c, hipEventRecord(l.ready, l.stream));
-        return PG_OK;
-    };
-    // fold the last finished chunk's shadow counts and kernel times into the statistics
-    auto collectStats = [&](Lane &l) -> pg_status {
-        if (!l.stats_pending) return PG_OK;
-        HIPC(c, hipEventSynchronize(l.done));
-        for (uint32_t k = 0; k < l.stats_bounces; ++k)
-            for (int sh = 0; sh < PG_QSHARDS; ++sh)
-            {
-                c->stats.shadow_rays += l.h_stats[(size_t)kBounceWords * k + kShadowCounts + sh];
-                c->probes += l.h_stats[(size_t)kBounceWords * k + kProbeCounts + sh];
-                // shadow rays the shader resolved: never queued, still shadow rays of the job
-                c->stats.shadow_rays += l.h_stats[(size_t)kBounceWords * k + kDropCounts + sh];
-                c->shadow_culled += l.h_stats[(size_t)kBounceWords * k + kDropCounts + sh];
-            }
-        c->stats.segments += l.h_tail[0];  // the chunk's tail (k_tail)
-        c->stats.escaped += l.h_tail[1];
-        c->stats.shadow_rays += l.h_tail[2];
-        c->culled += l.h_tail[3];
-        c->probes += l.h_tail[4];
-        c->shadow_culled += l.h_tail[5];
-        if (std::getenv("PG_DEBUG_COUNTS")) {
-            for (uint32_t k = 0; k < l.stats_bounces && k < l.used_prev.size(); ++k) {
-                uint64_t t = 0;
-                for (int w = 0; w < PG_CLASS_ROWS * PG_QSHARDS; ++w)
-                    t += l.h_stats[(size_t)kBounceWords * k + kClassCounts + w];
-                if (t != l.used_prev[k])
-                    std::fprintf(stderr, "PG_DEBUG_COUNTS: chunk bounce %u: host read %llu segments, device %llu\n", k,
-                                 (unsigned long long)l.used_prev[k], (unsigned long long)t);
-            }
-        }
-        const int prev = l.evcur ^ 1;
-        std::vector<EventPair> &pool = l.ev[prev];
-        for (size_t e = 0; e < l.evused[prev]; ++e) {
-            float ms = 0;
-            (void)hipEventElapsedTime(&ms, pool[e].a, pool[e].b);
-            switch (l.evkind[prev][e]) {
-                case KT_TRACE: c->stats.trace_ms += ms; c->stats.trace_launches++; break;
-                case KT_SHADE: c->stats.shade_ms += ms; break;
-                case KT_SHADOW: c->stats.shadow_ms += ms; c->stats.shadow_launches++; break;
-                default: c->stats.rays_ms += ms; c->stats.rays_launches++;
-            }
-        }
-        l.evused[prev] = 0;
-        l.stats_pending = false;
-        return PG_OK;
-    };
-    // start the next chunk on lane l (false: no chunks left)
-    auto startChunk = [&](Lane &l) -> pg_status {
-        l.active = false;
-        if (nextLayer >= spp) return PG_OK;
-        if (c->cancel.load()) return fail(c, PG_ERR_CANCELLED, "cancelled");
-        uint32_t nl = std::min(layersPer, spp - nextLayer);
-        if (npix > want) nl = 1;
-        const uint32_t pb = nextPix, np = std::min(pixPer, npix - pb);
-        l.layer0 = nextLayer;
-        l.pb = pb;
-        l.np = np;
-        l.nl = nl;
-        l.n = np * nl;
-        nextPix += np;
-        if (nextPix >= npix) {
-            nextPix = 0;
-            nextLayer += nl;
-        }
-        l.b = 0;
-        l.sorted = false;  // camera rays: their queue order is already coherent
-        l.bound = pg_camera_bound(pg_camera_banded(bands, l.np), l.np, l.nl);
-        l.active = true;
-        l.traced = false;
-        l.chunk = nextChunk++;
-        HIPC(c, hipStreamWaitEvent(l.stream, c->pass_start, 0));
-        HIPC(c, hipMemsetAsync(l.counters.p, 0, (size_t)kBounceWords * (maxBounces + 1) * 4, l.stream));
-        HIPC(c, hipMemsetAsync(l.tail_stats.p, 0, kTailStats * 8, l.stream));
-        pg_launch_camera(l.stream, g, pathView(&l), c->d_band_pixels.as<uint32_t>(), l.pb, l.np, l.nl,
-                         sample_offset + l.layer0, lqueue(l, l.q0.as<uint32_t>(), l.counters.as<uint32_t>()), bands);
-        return launchTrace(l, nullptr, nullptr);
-    };
-    // film + record commit (in chunk order across lanes), statistics copy; then the next chunk
-    auto finishChunk = [&](Lane &l) -> pg_status {
-        pg_status st;
-        if ((st = collectStats(l))) return st;
-        const PathDev pv = pathView(&l);
-        HIPC(c, hipMemcpyAsync(l.h_stats, l.counters.p, (size_t)kBounceWords * l.b * 4, hipMemcpyDeviceToHost, l.stream));
-        HIPC(c, hipMemcpyAsync(l.h_tail, l.tail_stats.p, kTailStats * 8, hipMemcpyDeviceToHost, l.stream));
-        HIPC(c, hipStreamWaitEvent(l.stream, c->film_order, 0));
-        pg_launch_film(l.stream, g, sc, pv, c->d_band_pixels.as<uint32_t>(), l.pb, l.np, l.nl, c->film.as<float4>(),
-                       c->film_sq.as<float4>(), c->aov_albedo.as<float4>(), c->aov_normal.as<float4>());
-        if (c->filtered)  // same chunk, same rows (the tail, when it ran, left them as the bounce launches do)
-            launchFilmFiltered(c, l.stream, g, sc, pv, c->d_band_pixels.as<uint32_t>(), l.pb, l.np, l.nl,
-                               sample_offset + l.layer0);
-        if (rec) {
-            // every slot can emit at most max_vertices records; grow the buffer (lanes idle) when the
-            // bound could overflow it
-            const uint64_t add = (uint64_t)l.n * g.max_vertices;
-            if (c->rec_bound + add > c->rec_capacity) {
-                for (int li = 0; li < c->nlanes; ++li) HIPC(c, hipStreamSynchronize(c->lanes[li].stream));
-                unsigned long long rc = 0;
-                HIPC(c, hipMemcpy(&rc, c->rec_count.p, 8, hipMemcpyDeviceToHost));
-                c->stats.records += rc - c->rec_host_count;
-                c->rec_host_count = c->rec_bound = rc;
-                if ((st = ensureRecords(c, rc + add))) return st;
-            }
-            c->rec_bound += add;
-            pg_launch_commit(l.stream, pv, l.n, g.max_vertices, c->records.as<pg_record>(),
-                             c->rec_count.as<unsigned long long>(), c->rec_capacity, c->has_env ? 1 : 0);
-        }
-        HIPC(c, hipEventRecord(c->film_order, l.stream));
-        HIPC(c, hipEventRecord(l.done, l.stream));
-        HIPC(c, hipGetLastError());
-        l.stats_pending = true;
-        l.stats_bounces = l.b;
-        l.used_prev.swap(l.used_cur);
-        l.used_cur.clear();
-        l.evcur ^= 1;
-        c->stats.paths += l.n;
-        return startChunk(l);
-    };
-    // one bounce's shading + shadow rays + next trace on lane l (class counts already on the host)
-    auto advance = [&](Lane &l) -> pg_status {
-        HIPC(c, hipEventSynchronize(l.ready));
-        uint32_t *cb = l.counters.as<uint32_t>() + (size_t)kBounceWords * l.b;
-        const uint32_t *hc = l.h_counts + (size_t)kBounceWords * l.b + kClassCounts;
-        uint32_t clsMax[PG_NUM_CLASSES], shardLive[PG_QSHARDS] = {};
-        uint64_t nlive = 0;
-        for (int k = 0; k < PG_CLASS_ROWS; ++k) {
-            uint32_t m = 0;
-            for (int sh = 0; sh < PG_QSHARDS; ++sh) {
-                const uint32_t v = hc[k * PG_QSHARDS + sh];
-                c->stats.segments += v;
-                if (k >= PG_NUM_CLASSES) {  // counted only: neither shaded nor alive
-                    (k == PG_CLASS_ESCAPED ? c->stats.escaped : c->culled) += v;
-                    continue;
-                }
-                m = std::max(m, v);
-                shardLive[sh] += v;
-                nlive += v;
-            }
-            if (k < PG_NUM_CLASSES) clsMax[k] = m;
-        }
-        {
-            uint64_t t = 0;
-            for (int w = 0; w < PG_CLASS_ROWS * PG_QSHARDS; ++w) t += hc[w];
-            l.used_cur.push_back(t);
-        }
-        ++l.b;
-        const uint32_t tailMax = c->cfg.tail_paths < 0 ? 0u : c->cfg.tail_paths > 0 ? (uint32_t)c->cfg.tail_paths : tailPaths();
-        const bool tail = nlive > 0 && nlive <= tailMax && l.b < maxBounces;
-        if (tail) {  // one launch finishes every remaining path (shading starts at the hits just traced)
-            const uint32_t *cbt = l.counters.as<uint32_t>() + (size_t)kBounceWords * (l.b - 1);
-            const Queue tq = lqueue(l, l.sorted ? l.qsorted.as<uint32_t>()
-                                                : ((l.b - 1) & 1) ? l.q1.as<uint32_t>() : l.q0.as<uint32_t>(),
-                                    const_cast<uint32_t *>(cbt));
-            pg_launch_tail(l.stream, g, sc, sd, pathView(&l), tq, l.bound, l.tail_stats.as<unsigned long long>());
-            c->stats.tail_launches += 1;
-        }
-        if (nlive == 0 || tail || l.b >= maxBounces) {
-            l.traced = true;
-            // finish this lane and every waiting lane whose turn comes after it, in chunk order
-            for (bool progress = true; progress;) {
-                progress = false;
-                for (Lane &o : c->lanes)
-                    if (o.active && o.traced && o.chunk == filmNext) {
-                        ++filmNext;
-                        pg_status st = finishChunk(o);
-                        if (st) return st;
-                        progress = true;
-                    }
-            }
-            return PG_OK;
-        }
-        Queue cls[PG_CLASS_ROWS];
-        classQueues(l, cb, cls);
-        const PathDev pv = pathView(&l);
-        Queue next = lqueue(l, (l.b & 1) ? l.q1.as<uint32_t>() : l.q0.as<uint32_t>(), cb + kBounceWords);
-        Queue shq = lqueue(l, l.qs.as<uint32_t>(), cb + kShadowCounts);
-        shq.dropped = cb + kDropCounts;
-        const Queue pq = lqueue(l, l.qp.as<uint32_t>(), cb + kProbeCounts);
-        const uint32_t nextBound = *std::max_element(shardLive, shardLive + PG_QSHARDS);
-        const bool sortNext = raySortEnabled() && nextBound >= kRaySortMinShard;
-        if (sortNext) next.keys = l.qkey.as<uint16_t>();
-        EventPair es{}, ew{};
-        if (evt) es = nextEvents(&l, KT_SHADE);
-        if (evt) HIPC(c, hipEventRecord(es.a, l.stream));
-        if (fuseShade) {  // one launch for every class present
-            pg_launch_shade_all(l.stream, g, sc, sd, pv, cls, clsMax, next, shq, pq);
-            c->stats.shade_launches += 1;
-        } else {
-            for (int k = 0; k < PG_NUM_CLASSES; ++k) {
-                pg_launch_shade_class(l.stream, k, g, sc, sd, pv, cls[k], clsMax[k], next, shq, pq);
-                c->stats.shade_launches += clsMax[k] ? 1 : 0;
-            }
-        }
-        if (evt) HIPC(c, hipEventRecord(es.b, l.stream));
-        l.bound = nextBound;
-        if (sortNext)  // group every shard of the next closest-hit queue by ray order key
-            pg_launch_ray_sort(l.stream, next, l.bound, l.qsorted.as<uint32_t>(), l.rsort_hist.as<uint32_t>());
-        l.sorted = sortNext;
-        // without per-launch timing the shadow rays share the next trace's launch
-        if (fuseRays) return launchTrace(l, &shq, &pq);
-        if (evt) ew = nextEvents(&l, KT_SHADOW);
-        if (evt) HIPC(c, hipEventRecord(ew.a, l.stream));
-        pg_launch_shadow(l.stream, g, sc, pv, shq, l.bound);
-        if (g.doom_probe) {  // the probes of this bounce, counted with the closest hits of the trace that follows
-            Queue ncls[PG_CLASS_ROWS];
-            classQueues(l, cb + kBounceWords, ncls);
-            pg_launch_probe(l.stream, sc, pv, pq, l.bound, ncls);
-        }
-        if (evt) HIPC(c, hipEventRecord(ew.b, l.stream));
-        return launchTrace(l, nullptr, nullptr);
-    };
-
-    for (int li = 0; li < c->nlanes; ++li)
-        if ((s = startChunk(c->lanes[li]))) return s;
-    // advance whichever lane has its counts first (waiting on a fixed lane order leaves the GPU idle
-    // whenever the other lane is already ready)
-    for (uint32_t rr = 0;; ++rr) {
-        int active = 0, picked = -1;
-        for (int k = 0; k < c->nlanes; ++k) {
-            Lane &l = c->lanes[(rr + k) % c->nlanes];
-            if (!l.active) continue;
-            ++active;
-            if (l.traced) continue;  // waiting for an earlier chunk's film
-            const hipError_t q = hipEventQuery(l.ready);
-            if (q == hipSuccess) {
-                picked = (int)((rr + k) % c->nlanes);
-                break;
-            }
-            if (q != hipErrorNotReady) HIPC(c, q);
-        }
-        if (!active) break;
-        if (picked >= 0 && (s = advance(c->lanes[picked]))) return s;
-    }
-    for (int li = 0; li < c->nlanes; ++li) {
-        Lane &l = c->lanes[li];
-        HIPC(c, hipStreamSynchronize(l.stream));
-        if ((s = collectStats(l))) return s;
-    }
-    if (rec) {
-        unsigned long long rc = 0;
-        HIPC(c, hipMemcpy(&rc, c->rec_count.p, 8, hipMemcpyDeviceToHost));
-        c->stats.records += rc - c->rec_host_count;
-        c->rec_host_count = c->rec_bound = rc;
-    }
-    HIPC(c, hipStreamSynchronize(c->stream));
-    if (learn && (s = learnBlockers(c))) return s;
-    return PG_OK;
-}
-
-// ProgressiveMonteCarloIntegrator::renderTime (progressiveintegrator.cpp:117-168): whole
-// progressions until the wall-clock budget is spent.  The reference checks the timer after every
-// progression of a 128-progression batch and cancels the rest; here consecutive progressions are
-// merged into one pg_render_pass (the film adds samples in sample order, so a merged pass equals
-// its progressions bit for bit), each merge covering at most half the remaining budget at the
-// measured rate, so the overshoot stays below one progression plus one readback.  Only whole
-// progressions reach the film: every pixel holds the same sample count (the reference may cancel
-// a progression midway, leaving some blocks with one progression more).
-pg_status pg_render_time(void *ctx, double seconds, uint32_t spp_per_progression, uint32_t sample_offset,
-                         uint32_t max_spp, uint32_t *spp_done) {
-    Ctx *c = (Ctx *)ctx;
-    if (!c || !spp_done) return fail(c, PG_ERR_INVALID, "pg_render_time: null argument");
-    *spp_done = 0;
-    if (!(seconds > 0) || spp_per_progression == 0)
-        return fail(c, PG_ERR_INVALID, "pg_render_time: need seconds > 0 and spp_per_progression > 0");
-    const uint32_t limit = max_spp ? max_spp : 0x7FFFFFFFu;
-    const auto t0 = std::chrono::steady_clock::now();
-    uint32_t done = 0, batch = std::min(spp_per_progression, limit);
-    while (done < limit) {
-        pg_status s = pg_render_pass(ctx, batch, sample_offset + done, 0);
-        if (s) return s;
-        done += batch;
-        *spp_done = done;
-        const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        if (el >= seconds) break;
-        const double perProg = el / (done / spp_per_progression);
-        const double progs = std::floor(0.5 * (seconds - el) / std::max(perProg, 1e-9));
-        const uint64_t want = (uint64_t)std::max(1.0, std::min(progs, 1e6)) * spp_per_progression;
-        batch = (uint32_t)std::min<uint64_t>(want, limit - done);
-        batch -= batch % spp_per_progression;  // whole progressions
-        if (batch == 0) break;
-    }
     return PG_OK;
 }
 

@@ -195,11 +195,13 @@ def test_small_chunks_bitexact(pg, paths):
             off += 2 ** it
         d.reset_film()
         d.render_pass(8, off, True)
-        out.append((d.read_film()[0], d.get_sdtree(), d.record_count(), d.stats()["paths"]))
+        st = d.stats()
+        out.append((d.read_film()[0], d.get_sdtree(), d.record_count(),
+                    tuple(st[k] for k in ("paths", "segments", "shadow_rays", "records"))))
         d.close()
     assert np.array_equal(out[0][0], out[1][0])
     assert np.array_equal(out[0][1], out[1][1])
-    assert out[0][2] == out[1][2] and out[0][3] == out[1][3]
+    assert out[0][2] == out[1][2] and out[0][3] == out[1][3], (out[0][3], out[1][3])
 
 
 def test_max_render_time(pg):
