@@ -521,6 +521,53 @@ pg_status pg_set_delta_emitters(void *ctx, const pg_delta_emitter *emitters, uin
  * out: n x 8 floats: d.xyz, dist, value / pdf (rgb, the emitter-pick probability included), measure (0 = the sample
  * failed, 1 = solid angle, 2 = discrete). */
 pg_status pg_emitter_query(void *ctx, const float *ref, const float *samples, uint64_t n, float *out);
+/* ---- homogeneous media: analytic free flight, chromatic extinction (volumetric integrator) --------------------------
+ * New entry points; pg_config, pg_stats, pg_scene_desc, pg_medium and PG_ABI_VERSION are unchanged.  While no record
+ * is set, no kernel compiled for them is launched and every result is bit for bit what it was.
+ *
+ * HomogeneousMedium with strategy = "balance" (homogeneous.cpp:266-352) as progressive_volpath.cpp:114-217 uses it,
+ * in float32 in this order, with sigma_t = sigma_a + sigma_s, exp = (float)exp((double)x) (math::fastexp) and log the
+ * tracking loops' logf:
+ *   weight: the given value; with -1, max over the channels with sigma_t != 0 of sigma_s / sigma_t, raised to 0.5
+ *           when that is > 0 (homogeneous.cpp:168-183)
+ *   sampleDistance on a ray with dist = maxt - mint:
+ *           rand = next1D;  if rand < weight: rand /= weight, channel = min((int)(next1D * 3), 2),
+ *           sampled = -log(1 - rand) / sigma_t[channel];  else sampled = +inf and no second draw
+ *           success = sampled < dist and o + d * (sampled + mint) != o;  where sampled >= dist, sampled = dist
+ *           pdfFailure = (sum_c exp(-sigma_t[c] sampled)) / 3,  pdfSuccess = (sum_c sigma_t[c] exp(-sigma_t[c] sampled)) / 3
+ *           pdfSuccess *= weight,  pdfFailure = weight pdfFailure + (1 - weight)
+ *           transmittance[c] = exp(-sigma_t[c] sampled), all three 0 when their maximum is < 1e-20
+ *   evalTransmittance: exp(sigma_t[c] (mint - maxt)) per channel, 1 where sigma_t[c] = 0; no draws
+ * A medium interaction multiplies the throughput by sigma_s transmittance / pdfSuccess, a flight that reaches the
+ * surface or escapes by transmittance / pdfFailure (a grid medium keeps its albedo).  The shadow walks of the
+ * next-event estimation and the emitter walks are chromatic per channel wherever they cross a homogeneous segment;
+ * such a segment consumes no draw of the walk's sub-stream and is not counted in pg_stats.density_lookups.  Direction
+ * guiding at medium vertices and training records work as in a grid medium; pg_config.distance_guiding does not apply
+ * inside a homogeneous medium: its flight is the analytic one above whatever beta is.  Not supported: the strategies
+ * single, manual and maximum, `monochromatic`, the material presets. */
+typedef struct pg_homogeneous_medium {
+    uint32_t medium;      /* index into the uploaded scene's media: the entry this record replaces */
+    float sigma_a[3];     /* after Medium::Medium's scale; >= 0 */
+    float sigma_s[3];
+    float g;              /* HG mean cosine, |g| < 1 */
+    float medium_sampling_weight; /* -1: the reference's rule (max channel albedo, raised to 0.5 when > 0) */
+    uint32_t pad0;
+} pg_homogeneous_medium;
+/* After pg_upload_scene and before the first render pass of that scene (PG_ERR_STATE otherwise); a later
+ * pg_upload_scene clears the records; n == 0 removes them, and the context is then bit for bit one on which the call
+ * was never made.  Each call replaces the whole set.  A replaced entry's grid, box, scale and albedo are ignored;
+ * shapes and camera_medium keep referring to it by index, and grid and homogeneous media may be mixed in one scene.
+ * PG_ERR_INVALID, with the state left as it was: the path integrator, an index out of range or named twice, a
+ * non-finite or negative coefficient, sigma_t = 0 in all three channels, |g| >= 1, a weight outside [0, 1] that is
+ * not -1.  pg_medium_query refuses a replaced entry (PG_ERR_INVALID); pg_phase_query answers with the record's g. */
+pg_status pg_set_homogeneous_media(void *ctx, const pg_homogeneous_medium *media, uint32_t n);
+/* Unit entry point (parity tests): the device functions the integrator calls, for the homogeneous medium `medium`.
+ * rays: n x 8 floats as pg_trace_rays (o.xyz, mint, d.xyz, maxt); keys: n x 2 (rng key, sample), the draws being
+ * dimensions 1, 2, ... of that counter stream as for pg_medium_query (not read by op 1).  out: n x 8 floats.
+ * op 0 (sampleDistance): success 1/0, t (mint + sampled; maxt where sampled >= dist), transmittance rgb, pdfSuccess,
+ *      pdfFailure, draws used.  op 1 (evalTransmittance): transmittance rgb, then zeros. */
+pg_status pg_homogeneous_query(void *ctx, uint32_t medium, int32_t op, const float *rays, const uint32_t *keys, uint64_t n,
+                               float *out);
 pg_status pg_get_stats(void *ctx, pg_stats *stats);
 /* Path integrator: segments (counted in pg_stats.segments, not in escaped) whose hit was culled by the
  * closest-hit kernels since create: the ray's next vertex had already lost its Russian roulette, or was past the

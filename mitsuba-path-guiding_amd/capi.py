@@ -84,6 +84,11 @@ class pg_delta_emitter(C.Structure):
                 ("intensity", C.c_float * 3), ("cutoff_angle", C.c_float), ("beam_width", C.c_float)]
 
 
+class pg_homogeneous_medium(C.Structure):
+    _fields_ = [("medium", C.c_uint32), ("sigma_a", C.c_float * 3), ("sigma_s", C.c_float * 3), ("g", C.c_float),
+                ("medium_sampling_weight", C.c_float), ("pad0", C.c_uint32)]
+
+
 class pg_camera(C.Structure):
     _fields_ = [("origin", C.c_float * 3), ("target", C.c_float * 3), ("up", C.c_float * 3),
                 ("fov_x_deg", C.c_float), ("near_clip", C.c_float), ("far_clip", C.c_float),
@@ -206,6 +211,8 @@ SIGNATURES = [
     ("pg_camera_rays", C.c_int32, [VP, VP, VP, C.c_uint32, VP, VP]),
     ("pg_set_delta_emitters", C.c_int32, [VP, C.POINTER(pg_delta_emitter), C.c_uint32]),
     ("pg_emitter_query", C.c_int32, [VP, VP, VP, C.c_uint64, VP]),
+    ("pg_set_homogeneous_media", C.c_int32, [VP, C.POINTER(pg_homogeneous_medium), C.c_uint32]),
+    ("pg_homogeneous_query", C.c_int32, [VP, C.c_uint32, C.c_int32, VP, VP, C.c_uint64, VP]),
     ("pg_get_stats", C.c_int32, [VP, C.POINTER(pg_stats)]),
     ("pg_get_culled", C.c_int32, [VP, C.POINTER(C.c_uint64)]),
     ("pg_get_probes", C.c_int32, [VP, C.POINTER(C.c_uint64)]),

@@ -198,6 +198,11 @@ struct Ctx {
     DevBuf delta;
     uint32_t num_delta = 0, num_area = 0;
     float tri_lo[3] = {0, 0, 0}, tri_hi[3] = {0, 0, 0};
+    // homogeneous media (pg_set_homogeneous_media): base_media is the uploaded scene's records, which `media` holds
+    // while num_homog is 0; is_homog marks the entries the records replaced
+    std::vector<GMedium> base_media;
+    std::vector<uint8_t> is_homog;
+    uint32_t num_homog = 0;
     // shard
     std::vector<uint32_t> local_pixels;
     DevBuf d_local_pixels;

@@ -1088,6 +1088,92 @@ pg_status pg_set_delta_emitters(void *ctx, const pg_delta_emitter *emitters, uin
     return resetBlockers(c);
 }
 
+// ---- homogeneous media (pg_capi.h pg_set_homogeneous_media) -----------------------------------------------------------
+pg_status pg_set_homogeneous_media(void *ctx, const pg_homogeneous_medium *media, uint32_t n) {
+    Ctx *c = (Ctx *)ctx;
+    if (!c) return fail(nullptr, PG_ERR_INVALID, "pg_set_homogeneous_media: null context");
+    if (!c->has_scene) return fail(c, PG_ERR_STATE, "pg_set_homogeneous_media: no scene uploaded");
+    if (c->scene_rendered)
+        return fail(c, PG_ERR_STATE, "pg_set_homogeneous_media: a render pass has already run on this scene");
+    if (c->cfg.integrator != PG_INTEGRATOR_VOLPATH)
+        return fail(c, PG_ERR_INVALID, "pg_set_homogeneous_media: the path integrator has no media");
+    if (n && !media) return fail(c, PG_ERR_INVALID, "pg_set_homogeneous_media: null argument");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    // validate everything before anything changes
+    std::vector<GMedium> recs = c->base_media;
+    std::vector<uint8_t> mark(c->num_media, 0);
+    for (uint32_t i = 0; i < n; ++i) {
+        const pg_homogeneous_medium &h = media[i];
+        const std::string id = "pg_set_homogeneous_media: record " + std::to_string(i) + ": ";
+        if (h.medium >= c->num_media) return fail(c, PG_ERR_INVALID, id + "medium index out of range");
+        if (mark[h.medium]) return fail(c, PG_ERR_INVALID, id + "medium named twice");
+        float sigmaT[3];
+        for (int k = 0; k < 3; ++k) {
+            if (!std::isfinite(h.sigma_a[k]) || !std::isfinite(h.sigma_s[k]))
+                return fail(c, PG_ERR_INVALID, id + "non-finite coefficient");
+            if (h.sigma_a[k] < 0 || h.sigma_s[k] < 0) return fail(c, PG_ERR_INVALID, id + "negative coefficient");
+            sigmaT[k] = h.sigma_a[k] + h.sigma_s[k];
+            if (!std::isfinite(sigmaT[k])) return fail(c, PG_ERR_INVALID, id + "non-finite coefficient");
+        }
+        if (sigmaT[0] == 0 && sigmaT[1] == 0 && sigmaT[2] == 0)
+            return fail(c, PG_ERR_INVALID, id + "sigma_t is zero in every channel");
+        if (!(std::fabs(h.g) < 1)) return fail(c, PG_ERR_INVALID, id + "|g| must be below 1");
+        float weight = h.medium_sampling_weight;
+        if (weight == -1.0f) {  // the reference's default (homogeneous.cpp:168-183)
+            weight = 0;
+            for (int k = 0; k < 3; ++k)
+                if (sigmaT[k] != 0) weight = std::max(weight, h.sigma_s[k] / sigmaT[k]);
+            if (weight > 0) weight = std::max(weight, 0.5f);
+        } else if (!(weight >= 0 && weight <= 1)) {
+            return fail(c, PG_ERR_INVALID, id + "medium_sampling_weight outside [0, 1] and not -1");
+        }
+        mark[h.medium] = 1;
+        GMedium &g = recs[h.medium];
+        g.density = nullptr;
+        g.maj = nullptr;
+        g.bx = 1;
+        g.g = h.g;
+        g.scale = weight;
+        for (int k = 0; k < 3; ++k) {
+            g.gs[k] = sigmaT[k];
+            g.go[k] = h.sigma_s[k];
+        }
+    }
+    if (c->num_media)
+        HIPC(c, hipMemcpy(c->media.p, recs.data(), recs.size() * sizeof(GMedium), hipMemcpyHostToDevice));
+    c->is_homog = mark;
+    c->num_homog = n;
+    return PG_OK;
+}
+
+pg_status pg_homogeneous_query(void *ctx, uint32_t medium, int32_t op, const float *rays, const uint32_t *keys, uint64_t n,
+                               float *out) {
+    Ctx *c = (Ctx *)ctx;
+    if (!c || (!rays && n) || (!out && n) || (op == 0 && !keys && n))
+        return fail(c, PG_ERR_INVALID, "pg_homogeneous_query: null argument");
+    if (op < 0 || op > 1) return fail(c, PG_ERR_INVALID, "pg_homogeneous_query: bad op");
+    if (!c->has_scene) return fail(c, PG_ERR_STATE, "pg_homogeneous_query: no scene");
+    if (medium >= c->num_media || !c->is_homog[medium])
+        return fail(c, PG_ERR_INVALID, "pg_homogeneous_query: not a homogeneous medium");
+    if (n > 0xFFFFFFFFull / 8) return fail(c, PG_ERR_INVALID, "pg_homogeneous_query: too many rays");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    if (!n) return PG_OK;
+    DevBuf a, k, o;
+    HIPC(c, a.alloc(n * 32));
+    HIPC(c, o.alloc(n * 32));
+    HIPC(c, hipMemcpyAsync(a.p, rays, n * 32, hipMemcpyHostToDevice, c->stream));
+    if (op == 0) {
+        HIPC(c, k.alloc(n * 8));
+        HIPC(c, hipMemcpyAsync(k.p, keys, n * 8, hipMemcpyHostToDevice, c->stream));
+    }
+    pg_launch_homog_query(c->stream, c->media.as<GMedium>() + medium, op, a.as<float>(),
+                          op == 0 ? k.as<uint32_t>() : nullptr, (uint32_t)n, o.as<float>());
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipMemcpyAsync(out, o.p, n * 32, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    return PG_OK;
+}
+
 pg_status pg_emitter_query(void *ctx, const float *ref, const float *samples, uint64_t n, float *out) {
     Ctx *c = (Ctx *)ctx;
     if (!c || (n && (!ref || !samples || !out))) return fail(c, PG_ERR_INVALID, "pg_emitter_query: null argument");
@@ -1354,6 +1440,10 @@ pg_status pg_upload_scene(void *ctx, const pg_scene_desc *d) {
         HIPC(c, hipStreamSynchronize(c->stream));  // the host density arrays are caller-owned
         if ((s = upload(c, c->media, gmed))) return s;
         c->num_media = d->num_media;
+        // a new scene has no homogeneous media (pg_set_homogeneous_media)
+        c->base_media = gmed;
+        c->is_homog.assign(d->num_media, 0);
+        c->num_homog = 0;
         c->cam_medium = d->camera_medium;
     }
 
@@ -2041,6 +2131,8 @@ pg_status pg_medium_query(void *ctx, uint32_t medium, int32_t op, const float *i
     if (op < 0 || op > 4) return fail(c, PG_ERR_INVALID, "pg_medium_query: bad op");
     if (!c->has_scene) return fail(c, PG_ERR_STATE, "pg_medium_query: no scene");
     if (medium >= c->num_media) return fail(c, PG_ERR_INVALID, "pg_medium_query: bad medium");
+    if (c->is_homog[medium])
+        return fail(c, PG_ERR_INVALID, "pg_medium_query: a homogeneous medium has no grid (pg_homogeneous_query)");
     HIPC(c, hipSetDevice(c->cfg.device));
     if (!n) return PG_OK;
     const size_t inBytes = n * (op == 0 ? 12 : 32), outBytes = n * (op == 0 ? 4 : 16);

@@ -98,6 +98,7 @@ struct VolDev {
     uint32_t refill_min;       // k_volpath refills a wave's finished lanes once at least this many are idle
     const uint8_t *tcheap;     // per BVH-order triangle: 1 = delta BSDF or emitter (the wavefront's cheap surface queue)
     uint32_t models;           // 1: every material is diffuse or null (surface launches compiled for those only)
+    uint32_t homog;            // 1: homogeneous media are set (pg_set_homogeneous_media): the HOMOG instantiations
 };
 
 // Volumetric wavefront (pg_volpath.hip k_vcam, k_vflight, k_vvertex, k_vtail): the megakernel's per-lane
@@ -286,6 +287,9 @@ void pg_launch_phase_query(hipStream_t s, const GMedium *medium, const float *in
                            float *out);
 // corner-packed density of a linear grid (pg_layout.h "Corner-packed density"); out: 8 floats per cell
 void pg_launch_density_corners(hipStream_t s, const float *lin, uint32_t rx, uint32_t ry, uint32_t rz, float *out);
+// unit-level homogeneous medium (pg_homogeneous_query): op 0 sampleDistance, 1 evalTransmittance; 8 floats per ray
+void pg_launch_homog_query(hipStream_t s, const GMedium *medium, int op, const float *in, const uint32_t *keys,
+                           uint32_t n, float *out);
 void pg_launch_medium_query(hipStream_t s, const GMedium *medium, int op, const float *in, const uint32_t *keys,
                             uint32_t n, float *out);
 void pg_launch_trace_rays(hipStream_t s, const SceneDev &sc, const float *rays, uint32_t n, int any, float *hits,

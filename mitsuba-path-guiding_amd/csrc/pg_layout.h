@@ -95,6 +95,10 @@ static_assert(sizeof(GTex) == 64, "GTex layout");
 // (gridvolume.cpp:583-585, heterogeneous.cpp:236-242).  density: res x*y*z floats, x fastest.
 // maj: the majorant grid, mx*my*mz cells of PG_MAJORANT_CELL^3 voxels, each scale * the maximum
 // voxel over the cell extended by one voxel per side.
+// A homogeneous entry (pg_set_homogeneous_media; pg_volpath.hip "homogeneous medium") reuses the record, so VolDev::media
+// stays one array indexed by the shapes' medium ids: bx = 1 marks it, gs holds sigma_t, go sigma_s and scale the
+// medium sampling weight; g, lo and hi keep their meaning (lo / hi: the flight queue's order key only), the other
+// grid fields are not read.
 #ifndef PG_MAJORANT_CELL
 #define PG_MAJORANT_CELL 16  // voxels per majorant cell and axis (oracle: orc_medium.h kCell)
 #endif
@@ -110,7 +114,7 @@ struct GMedium {
     float gs[3];
     uint32_t mz;
     float go[3];
-    uint32_t bx;  // unused (0)
+    uint32_t bx;  // 1: a homogeneous entry (above); 0: a density grid
     float albedo[3];
     uint32_t by;  // unused (0)
     const float *maj;

@@ -431,6 +431,7 @@ pg_status renderVolpath(Ctx *c, uint32_t spp, uint32_t sample_offset, bool rec) 
     }
     v.cam_medium = c->cam_medium;
     v.num_media = c->num_media;
+    v.homog = c->num_homog ? 1u : 0u;  // the launchers' HOMOG instantiations (pg_set_homogeneous_media)
     v.rad = c->vol_rad.as<float4>();
     v.next = c->vol_work.as<uint32_t>();
     v.stats = (unsigned long long *)(c->vol_work.as<uint8_t>() + 16);

@@ -387,6 +387,81 @@ __device__ __forceinline__ float mediumTransmittance(const VolDev &v, int m, f3 
     return v.grid ? evalTransmittanceGrid(M, o, d, maxt, rng) : evalTransmittance(M, o, d, maxt, rng);
 }
 
+// ---- homogeneous medium (homogeneous.cpp:266-352, strategy = balance) --------------------------
+// HOMOG: homogeneous records are set (pg_set_homogeneous_media; VolDev::homog): the per-medium type test, the
+// analytic free flight and the chromatic transmittance; with HOMOG = false none of it is compiled and a
+// transmittance is one float.  A homogeneous entry of VolDev::media keeps its record's box (flightKey) and
+// g, and holds sigma_t in gs, sigma_s in go, the medium sampling weight in scale and 1 in bx (pg_layout.h).
+template <bool HOMOG>
+using VTr = std::conditional_t<HOMOG, f3, float>;
+template <bool HOMOG>
+__device__ __forceinline__ VTr<HOMOG> transOf(float x) {
+    if constexpr (HOMOG) return mk1(x);
+    else return x;
+}
+__device__ __forceinline__ bool zeroT(float T) { return T == 0; }
+__device__ __forceinline__ bool zeroT(f3 T) { return isZero(T); }
+__device__ __forceinline__ bool isHomog(const GMedium &G) { return G.bx != 0; }
+__device__ __forceinline__ f3 homogExp(f3 sigmaT, float x) {  // exp(sigma_t x) per channel
+    return mk(fastexp(sigmaT.x * x), fastexp(sigmaT.y * x), fastexp(sigmaT.z * x));
+}
+// evalTransmittance: exact, no draws
+__device__ __forceinline__ f3 homogTransmittance(const GMedium &G, float mint, float maxt) {
+    const f3 sigmaT = mk(G.gs[0], G.gs[1], G.gs[2]);
+    const float negLength = mint - maxt;
+    const f3 e = homogExp(sigmaT, negLength);
+    return mk(sigmaT.x != 0 ? e.x : 1.0f, sigmaT.y != 0 ? e.y : 1.0f, sigmaT.z != 0 ? e.z : 1.0f);
+}
+struct HomSample {
+    float t;  // the distance from the ray's origin (mint + the sampled distance)
+    f3 tr;
+    float pdfSuccess, pdfFailure;
+};
+// sampleDistance: one draw for the medium sampling weight, one for the channel when it scatters
+__device__ __forceinline__ bool homogSampleDistance(const GMedium &G, f3 o, f3 d, float mint, float maxt, VRng &rng,
+                                                    HomSample &s) {
+    const f3 sigmaT = mk(G.gs[0], G.gs[1], G.gs[2]);
+    const float weight = G.scale;
+    float rand = rng.next1(), sampled;
+    if (rand < weight) {
+        rand /= weight;
+        const int channel = min((int)(rng.next1() * 3), 2);
+        sampled = -trackLog(1 - rand) / (channel == 0 ? sigmaT.x : (channel == 1 ? sigmaT.y : sigmaT.z));
+    } else {
+        sampled = __int_as_float(0x7f800000);
+    }
+    const float dist = maxt - mint;
+    bool success = true;
+    if (sampled < dist) {
+        s.t = sampled + mint;
+        const f3 p = o + d * s.t;
+        if (p.x == o.x && p.y == o.y && p.z == o.z) success = false;  // no forward progress
+    } else {
+        sampled = dist;
+        s.t = maxt;
+        success = false;
+    }
+    const f3 e = homogExp(sigmaT, -sampled);
+    s.pdfFailure = (e.x + e.y + e.z) / 3.0f;
+    s.pdfSuccess = (sigmaT.x * e.x + sigmaT.y * e.y + sigmaT.z * e.z) / 3.0f;
+    s.tr = e;
+    s.pdfSuccess = s.pdfSuccess * weight;
+    s.pdfFailure = weight * s.pdfFailure + (1 - weight);
+    if (maxc(s.tr) < 1e-20f) s.tr = mk1(0.0f);
+    return success;
+}
+// Medium::evalTransmittance of medium m over [0, maxt]: a homogeneous segment makes no draw and no lookup
+template <bool HOMOG>
+__device__ __forceinline__ VTr<HOMOG> mediumTransmittanceT(const VolDev &v, int m, f3 o, f3 d, float maxt, VRng &rng) {
+    if constexpr (HOMOG) {
+        const GMedium &G = v.media[m];
+        if (isHomog(G)) return homogTransmittance(G, 0.0f, maxt);
+        return mk1(mediumTransmittance(v, m, o, d, maxt, rng));
+    } else {
+        return mediumTransmittance(v, m, o, d, maxt, rng);
+    }
+}
+
 // ---- scene queries ----------------------------------------------------------------------------
 // o + d t, the multiply and the add rounded separately as in the oracle (orc_volpath.h, built with
 // -ffp-contract=off): the emitter walk's second pass must reproduce its first pass's origins bit for bit,
@@ -425,7 +500,8 @@ __device__ __forceinline__ f3 rawFaceNormal(const SceneDev &sc, uint32_t tri) {
 }
 
 // Scene::evalTransmittance (scene.cpp:662-720) from p1 to a point p2 on an emitter
-__device__ __forceinline__ float sceneTransmittance(const SceneDev &sc, const VolDev &v, f3 p1, bool p1OnSurface, f3 p2, int medium,
+template <bool HOMOG = false>
+__device__ __forceinline__ VTr<HOMOG> sceneTransmittance(const SceneDev &sc, const VolDev &v, f3 p1, bool p1OnSurface, f3 p2, int medium,
                                     int maxInteractions, VRng &rng, const TStack &stk, uint32_t &segs) {
     f3 d = p2 - p1;
     float remaining = len(d);
@@ -434,7 +510,7 @@ __device__ __forceinline__ float sceneTransmittance(const SceneDev &sc, const Vo
     f3 o = p1;
     float mint = p1OnSurface ? kEpsilon * max3abs(o) : 0.0f;  // rayIntersect(ray, t, shape, n, uv) rule
     float maxt = remaining * lengthFactor;
-    float T = 1.0f;
+    VTr<HOMOG> T = transOf<HOMOG>(1.0f);
     int interactions = 0;
     while (remaining > 0) {
         float t, u, w;
@@ -442,14 +518,14 @@ __device__ __forceinline__ float sceneTransmittance(const SceneDev &sc, const Vo
         const bool surface = closestHit(sc, o, d, mint, maxt, t, tri, u, w, stk);
         segs++;
         if (!surface) t = __int_as_float(0x7f800000);
-        if (surface && (interactions == maxInteractions || !isNullMat(sc, triBits(sc, tri)))) return 0.0f;
-        if (medium >= 0) T *= mediumTransmittance(v, medium, o, d, fminf(t, remaining), rng);
-        if (!surface || T == 0) break;
+        if (surface && (interactions == maxInteractions || !isNullMat(sc, triBits(sc, tri)))) return transOf<HOMOG>(0.0f);
+        if (medium >= 0) T = T * mediumTransmittanceT<HOMOG>(v, medium, o, d, fminf(t, remaining), rng);
+        if (!surface || zeroT(T)) break;
         if (!VCHK(tri != 0xFFFFFFFFu, 2, interactions)) break;
         const uint32_t tm = v.tmed[tri];
         if (tm) {
             const f3 n = rawFaceNormal(sc, tri);
-            if (medium != targetMedium(tm, -d, n)) return 0.0f;
+            if (medium != targetMedium(tm, -d, n)) return transOf<HOMOG>(0.0f);
             medium = targetMedium(tm, d, n);
         }
         if (++interactions > 100) break;
@@ -523,9 +599,10 @@ __device__ __forceinline__ void lookForEmitter(const SceneDev &sc, const VolDev 
 }
 // the transmittance of an emitter walk's segments in media: the walk's rays again (origins advanced the
 // same way, so the same surfaces), tracking every segment in a medium on the walk's sub-stream
-__device__ __forceinline__ float emitterWalkT(const SceneDev &sc, const VolDev &v, int medium, int interactions, f3 o0,
+template <bool HOMOG = false>
+__device__ __forceinline__ VTr<HOMOG> emitterWalkT(const SceneDev &sc, const VolDev &v, int medium, int interactions, f3 o0,
                                               f3 d, float mint0, VRng &rng, const TStack &stk, uint32_t &segs) {
-    float T = 1.0f;
+    VTr<HOMOG> T = transOf<HOMOG>(1.0f);
     f3 oo = o0;
     float mt = mint0;
     int mm = medium;
@@ -537,10 +614,10 @@ __device__ __forceinline__ float emitterWalkT(const SceneDev &sc, const VolDev &
         // the re-walk repeats the first walk's rays, so it hits the same surfaces; were a rounding
         // difference to make it miss, tr would be ~0 and v.tmed[tr] / fetchHit would read 16 GB
         // past their arrays (the round-3 C5 faults): end the estimate instead
-        if (!VCHK(hitR, 1, k)) return 0.0f;
+        if (!VCHK(hitR, 1, k)) return transOf<HOMOG>(0.0f);
         if (mm >= 0) {
-            T *= mediumTransmittance(v, mm, oo, d, tt, rng);
-            if (T == 0) break;
+            T = T * mediumTransmittanceT<HOMOG>(v, mm, oo, d, tt, rng);
+            if (zeroT(T)) break;
         }
         const uint32_t tm = v.tmed[tr];
         if (tm) {
@@ -654,10 +731,27 @@ __device__ __forceinline__ void deferHit(VDefer &df, const VolWave &w, uint32_t 
 __device__ __forceinline__ bool volDepthOk(const GParams &g, const VPath &P) {
     return (P.depth <= g.max_depth || g.max_depth < 0) && P.depth <= g.depth_cap;
 }
-template <bool GUIDED>
+// HOMOG: in a homogeneous medium (pg_set_homogeneous_media) the flight is analytic whatever distance_guiding is, and
+// the throughput takes sigma_s * transmittance / pdfSuccess at a medium interaction and transmittance / pdfFailure
+// when the flight reaches the surface or escapes (progressive_volpath.cpp:133, :204)
+template <bool GUIDED, bool HOMOG = false>
 __device__ __forceinline__ bool volFlight(const VolDev &v, const SDDev &sd, VPath &P, VRng &rng, f3 &mp) {
     const bool guiding = GUIDED && sd.built;
     const float maxt = P.its.valid ? P.its.t : __int_as_float(0x7f800000);
+    if constexpr (HOMOG) {
+        const GMedium &G = v.media[P.medium];
+        if (isHomog(G)) {
+            HomSample s;
+            const bool inMedium = homogSampleDistance(G, P.o, P.d, 0.0f, maxt, rng, s);
+            if (inMedium) {
+                mp = P.o + P.d * s.t;
+                P.T = P.T * ((mk(G.go[0], G.go[1], G.go[2]) * s.tr) / s.pdfSuccess);
+            } else {
+                P.T = P.T * (s.tr / s.pdfFailure);
+            }
+            return inMedium;
+        }
+    }
     if (guiding && v.dist_beta > 0) {
         float w;
         const bool inMedium = mediumSampleGuided(v, sd, P.medium, P.o, P.d, maxt, rng, mp, w);
@@ -678,7 +772,7 @@ __device__ __forceinline__ bool volRoulette(const GParams &g, VPath &P, VRng &rn
 }
 // DELTA: delta emitters are set (pg_set_delta_emitters; SceneDev::delta): sampleEmitter's point / spot / directional
 // branches and the discrete-measure rule of the NEE; with DELTA = false none of it is compiled.
-template <bool GUIDED, bool SINK, bool DELTA = false>
+template <bool GUIDED, bool SINK, bool DELTA = false, bool HOMOG = false>
 __device__ __forceinline__ bool volMedium(const GParams &g, const SceneDev &sc, const VolDev &v, const SDDev &sd,
                                           VPath &P, VRng &rng, const TStack &stk, uint32_t item, uint32_t &segs,
                                           uint32_t &shadows, f3 mp, VDefer &df, const VolWave &wk) {
@@ -691,7 +785,8 @@ __device__ __forceinline__ bool volMedium(const GParams &g, const SceneDev &sc, 
         // ---- medium interaction (progressive_volpath.cpp:117-196)
         if (P.depth >= maxDepth && maxDepth != -1) return false;
         const GMedium &GM = v.media[P.medium];
-        P.T = P.T * mk(GM.albedo[0], GM.albedo[1], GM.albedo[2]);
+        if (!(HOMOG && isHomog(GM)))  // a homogeneous medium's sigma_s is in its flight's weight (volFlight)
+            P.T = P.T * mk(GM.albedo[0], GM.albedo[1], GM.albedo[2]);
         const float hg = GM.g;
         const f3 wi = -P.d;
         const SDView sv = sdv(sd);
@@ -932,25 +1027,27 @@ __device__ __forceinline__ bool volSurface(const GParams &g, const SceneDev &sc,
 // an interaction's deferred walks, in the oracle's order: the emitter hit, then the NEE (into L and into
 // the snapshot of the interaction's training vertex); each on its own sub-stream of the path's key
 // the walks' transmittances, each on its sub-stream (no radiance touched yet)
+template <bool HOMOG = false>
 __device__ __forceinline__ void walkDeferred(const SceneDev &sc, const VolDev &v, const VDefer &df, uint32_t key,
                                              uint32_t sample, const TStack &stk, uint32_t &segs, uint32_t &lookups,
-                                             float &Th, float &Tn) {
-    Th = Tn = 0.0f;
+                                             VTr<HOMOG> &Th, VTr<HOMOG> &Tn) {
+    Th = Tn = transOf<HOMOG>(0.0f);
     if (df.hit) {
         VRng sub = subStream(key, sample, df.hDim, 1);
-        Th = emitterWalkT(sc, v, df.hMedium, df.hInter, df.hO, df.hD, df.hMint, sub, stk, segs);
+        Th = emitterWalkT<HOMOG>(sc, v, df.hMedium, df.hInter, df.hO, df.hD, df.hMint, sub, stk, segs);
         lookups += sub.lookups;
     }
     if (df.nee) {
         VRng sub = subStream(key, sample, df.nDim, 0);
-        Tn = sceneTransmittance(sc, v, df.n1, df.nOnSurface, df.n2, df.nMedium, df.nMaxInter, sub, stk, segs);
+        Tn = sceneTransmittance<HOMOG>(sc, v, df.n1, df.nOnSurface, df.n2, df.nMedium, df.nMaxInter, sub, stk, segs);
         lookups += sub.lookups;
     }
 }
 // their contributions, in the fixed order: the emitter hit, then the NEE (also into the vertex's snapshot)
-__device__ __forceinline__ void addDeferred(const VolDev &v, const VDefer &df, float Th, float Tn, uint32_t item, f3 &L) {
-    if (df.hit && Th != 0) L = L + df.hC * Th;
-    if (df.nee && Tn != 0) {
+template <class TR>  // float, or f3 with homogeneous media
+__device__ __forceinline__ void addDeferred(const VolDev &v, const VDefer &df, TR Th, TR Tn, uint32_t item, f3 &L) {
+    if (df.hit && !zeroT(Th)) L = L + df.hC * Th;
+    if (df.nee && !zeroT(Tn)) {
         const f3 add = df.nC * Tn;
         L = L + add;
         if (df.k >= 0) {
@@ -959,11 +1056,12 @@ __device__ __forceinline__ void addDeferred(const VolDev &v, const VDefer &df, f
         }
     }
 }
+template <bool HOMOG = false>
 __device__ __forceinline__ void resolveDeferred(const SceneDev &sc, const VolDev &v, const VDefer &df, uint32_t key,
                                                 uint32_t sample, uint32_t item, f3 &L, const TStack &stk,
                                                 uint32_t &segs, uint32_t &lookups) {
-    float Th, Tn;
-    walkDeferred(sc, v, df, key, sample, stk, segs, lookups, Th, Tn);
+    VTr<HOMOG> Th, Tn;
+    walkDeferred<HOMOG>(sc, v, df, key, sample, stk, segs, lookups, Th, Tn);
     addDeferred(v, df, Th, Tn, item, L);
 }
 __device__ __forceinline__ void clearDefer(VDefer &df) {
@@ -971,27 +1069,27 @@ __device__ __forceinline__ void clearDefer(VDefer &df) {
     df.k = -1;
 }
 
-template <bool GUIDED, int MODELS = -1, bool DELTA = false>
+template <bool GUIDED, int MODELS = -1, bool DELTA = false, bool HOMOG = false>
 __device__ __forceinline__ bool volStep(const GParams &g, const SceneDev &sc, const VolDev &v, const SDDev &sd,
                                         VPath &P, VRng &rng, const TStack &stk, uint32_t item, uint32_t &segs,
                                         uint32_t &shadows, VDefer &df) {
     if (!volDepthOk(g, P)) return false;
     f3 mp = mk1(0.f);
     const VolWave none{};
-    if (P.medium >= 0 && volFlight<GUIDED>(v, sd, P, rng, mp))
-        return volMedium<GUIDED, false, DELTA>(g, sc, v, sd, P, rng, stk, item, segs, shadows, mp, df, none);
+    if (P.medium >= 0 && volFlight<GUIDED, HOMOG>(v, sd, P, rng, mp))
+        return volMedium<GUIDED, false, DELTA, HOMOG>(g, sc, v, sd, P, rng, stk, item, segs, shadows, mp, df, none);
     return volSurface<GUIDED, false, MODELS, DELTA>(g, sc, v, sd, P, rng, stk, item, segs, shadows, df, none);
 }
 // one step with its walks resolved right away (k_vtail, k_volpath): the same arithmetic as the wavefront's
 // k_vvertex + k_vnee
-template <bool GUIDED, int MODELS = -1, bool DELTA = false>
+template <bool GUIDED, int MODELS = -1, bool DELTA = false, bool HOMOG = false>
 __device__ __forceinline__ bool volStepResolved(const GParams &g, const SceneDev &sc, const VolDev &v, const SDDev &sd,
                                                 VPath &P, VRng &rng, const TStack &stk, uint32_t item, uint32_t &segs,
                                                 uint32_t &shadows) {
     VDefer df;
     clearDefer(df);
-    const bool alive = volStep<GUIDED, MODELS, DELTA>(g, sc, v, sd, P, rng, stk, item, segs, shadows, df);
-    if (df.hit || df.nee) resolveDeferred(sc, v, df, rng.key, rng.sample, item, P.L, stk, segs, rng.lookups);
+    const bool alive = volStep<GUIDED, MODELS, DELTA, HOMOG>(g, sc, v, sd, P, rng, stk, item, segs, shadows, df);
+    if (df.hit || df.nee) resolveDeferred<HOMOG>(sc, v, df, rng.key, rng.sample, item, P.L, stk, segs, rng.lookups);
     return alive;
 }
 
@@ -1210,7 +1308,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) void k_vcam(GParams g, SceneDev sc, Vo
 #ifndef PG_VVERTEX_WAVES
 #define PG_VVERTEX_WAVES PG_VOL_WAVES
 #endif
-template <bool GUIDED>
+template <bool GUIDED, bool HOMOG = false>
 __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PG_VFLIGHT_WAVES > 0 ? PG_VFLIGHT_WAVES : 1)))
 void k_vflight(GParams g, SceneDev sc, VolDev v, SDDev sd, VolWave w, Queue qf, Queue qm, Queue qs, Queue qd) {
     const uint32_t sh = blockIdx.x & (PG_QSHARDS - 1), rows = gridDim.x / PG_QSHARDS;
@@ -1230,11 +1328,12 @@ void k_vflight(GParams g, SceneDev sc, VolDev v, SDDev sd, VolWave w, Queue qf, 
             P.its.valid = ((s.z >> 16) & 1u) != 0;
             P.its.t = o.w;
             P.medium = (int)(s.z & 0xFFFFu) - 1;
-            const bool wT = GUIDED && sd.built && v.dist_beta > 0;  // guided free flight reweights T
+            // guided free flight reweights T, and so does a homogeneous medium's
+            const bool wT = (GUIDED && sd.built && v.dist_beta > 0) || (HOMOG && isHomog(v.media[P.medium]));
             if (wT) P.T = xyz(w.T[slot]);
             VRng rng{r.x, r.y, r.z, r.w};
             f3 mp = mk1(0.f);
-            toM = volFlight<GUIDED>(v, sd, P, rng, mp);
+            toM = volFlight<GUIDED, HOMOG>(v, sd, P, rng, mp);
             toS = !toM;
             if (toS) cheap = cheapSurface(sc, v, P.its.valid, s.y);
             flights++;
@@ -1281,7 +1380,7 @@ struct VVertexWaves {
                                            : (KIND == 1 || KIND == 3 ? (NEE_STAGE ? PG_VSURFACE_WAVES : PG_VSURFACE_INLINE_WAVES)
                                                         : PG_VVERTEX_WAVES);
 };
-template <bool GUIDED, bool NEE_STAGE, int KIND, bool DELTA = false>
+template <bool GUIDED, bool NEE_STAGE, int KIND, bool DELTA = false, bool HOMOG = false>
 __global__ __launch_bounds__(TRACE_BLOCK, (VVertexWaves<NEE_STAGE, KIND>::value)) void k_vvertex(GParams g, SceneDev sc, VolDev v, SDDev sd,
                                                                        VolWave w, Queue qm, Queue qs, Queue qd,
                                                                        uint32_t mblocks, uint32_t dblocks, Queue nf,
@@ -1312,7 +1411,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, (VVertexWaves<NEE_STAGE, KIND>::value)
             clearDefer(df);
             bool alive;
             if (KIND == 0 || (KIND == 2 && medium))
-                alive = volMedium<GUIDED, NEE_STAGE, DELTA>(g, sc, v, sd, P, rng, stk, slot, segs, shadows, xyz(w.mp[slot]), df, w);
+                alive = volMedium<GUIDED, NEE_STAGE, DELTA, HOMOG>(g, sc, v, sd, P, rng, stk, slot, segs, shadows, xyz(w.mp[slot]), df, w);
             else
                 alive = volSurface<GUIDED, NEE_STAGE, KIND == 3 ? PG_MODELS_DIFFUSE_NULL : -1, DELTA>(g, sc, v, sd, P, rng, stk,
                                                                                           slot, segs, shadows, df, w);
@@ -1335,9 +1434,9 @@ __global__ __launch_bounds__(TRACE_BLOCK, (VVertexWaves<NEE_STAGE, KIND>::value)
                     w.nflags[slot] = make_uint4(deferFlags(df, ended), key0, sample0, 0u);
                     toN = true;
                 } else {  // inline: the walks, then their adds into the stored radiance (the same order and sums)
-                    float Th, Tn;
+                    VTr<HOMOG> Th, Tn;
                     uint32_t wl = 0;
-                    walkDeferred(sc, v, df, key0, sample0, stk, segs, wl, Th, Tn);
+                    walkDeferred<HOMOG>(sc, v, df, key0, sample0, stk, segs, wl, Th, Tn);
                     lookups += wl;
                     vlookups += wl;
                     float4 *dst = ended ? v.rad + slot : w.L + slot;
@@ -1362,7 +1461,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, (VVertexWaves<NEE_STAGE, KIND>::value)
 #ifndef PG_VNEE_WAVES
 #define PG_VNEE_WAVES 3
 #endif
-template <bool GUIDED>
+template <bool GUIDED, bool HOMOG = false>
 __global__ __launch_bounds__(TRACE_BLOCK, PG_VNEE_WAVES) void k_vnee(GParams g, SceneDev sc, VolDev v, VolWave w, Queue qn) {
     __shared__ uint32_t stack[LDS_STACK * TRACE_BLOCK];
     const TStack stk = threadStack(stack, v.stack_ovf);
@@ -1378,7 +1477,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, PG_VNEE_WAVES) void k_vnee(GParams g, 
         float4 *dst = ended ? v.rad + slot : w.L + slot;
         const float4 l4 = *dst;
         f3 L = xyz(l4);
-        resolveDeferred(sc, v, df, key, sample, slot, L, stk, segs, lookups);
+        resolveDeferred<HOMOG>(sc, v, df, key, sample, slot, L, stk, segs, lookups);
         *dst = f4(L, l4.w);
         walks++;
     }
@@ -1391,7 +1490,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, PG_VNEE_WAVES) void k_vnee(GParams g, 
 #ifndef PG_VTAIL_WAVES
 #define PG_VTAIL_WAVES 3  // C5 442.3 / 441.9 against 439.2 / 439.6 at 2 (profiles/r05q_vol_waves/)
 #endif
-template <bool GUIDED, int MODELS, bool DELTA = false>
+template <bool GUIDED, int MODELS, bool DELTA = false, bool HOMOG = false>
 __global__ __launch_bounds__(TRACE_BLOCK, PG_VTAIL_WAVES) void k_vtail(GParams g, SceneDev sc, VolDev v, SDDev sd,
                                                                      VolWave w, Queue qf, Queue qs, Queue qd,
                                                                      uint32_t fblocks, uint32_t dblocks) {
@@ -1415,9 +1514,9 @@ __global__ __launch_bounds__(TRACE_BLOCK, PG_VTAIL_WAVES) void k_vtail(GParams g
             VDefer df;
             clearDefer(df);
             alive = volSurface<GUIDED, false, MODELS, DELTA>(g, sc, v, sd, P, rng, stk, slot, segs, shadows, df, w);
-            if (df.hit || df.nee) resolveDeferred(sc, v, df, rng.key, rng.sample, slot, P.L, stk, segs, rng.lookups);
+            if (df.hit || df.nee) resolveDeferred<HOMOG>(sc, v, df, rng.key, rng.sample, slot, P.L, stk, segs, rng.lookups);
         }
-        while (alive) alive = volStepResolved<GUIDED, MODELS, DELTA>(g, sc, v, sd, P, rng, stk, slot, segs, shadows);
+        while (alive) alive = volStepResolved<GUIDED, MODELS, DELTA, HOMOG>(g, sc, v, sd, P, rng, stk, slot, segs, shadows);
         volEnd(v, slot, P, rng, lookups);
     }
     volStats(v, segs, shadows, lookups);
@@ -1451,10 +1550,15 @@ void pg_launch_vol_flight(hipStream_t s, const GParams &g, const SceneDev &sc, c
                           const VolWave &w, Queue flight, uint32_t max_flight, Queue med, Queue surf, Queue dsurf) {
     if (!max_flight) return;
     const dim3 grid(PG_QSHARDS * vrows(max_flight, TRACE_MAX_BLOCKS / PG_QSHARDS));
-    if (g.guiding)
-        hipLaunchKernelGGL(k_vflight<true>, grid, dim3(TRACE_BLOCK), 0, s, g, sc, v, sd, w, flight, med, surf, dsurf);
-    else
-        hipLaunchKernelGGL(k_vflight<false>, grid, dim3(TRACE_BLOCK), 0, s, g, sc, v, sd, w, flight, med, surf, dsurf);
+#define PG_VF(GU, HO) \
+    hipLaunchKernelGGL((k_vflight<GU, HO>), grid, dim3(TRACE_BLOCK), 0, s, g, sc, v, sd, w, flight, med, surf, dsurf)
+    // v.homog: homogeneous media are set (pg_set_homogeneous_media); scenes without them launch the kernels they always did
+    if (v.homog) {
+        if (g.guiding) PG_VF(true, true); else PG_VF(false, true);
+    } else {
+        if (g.guiding) PG_VF(true, false); else PG_VF(false, false);
+    }
+#undef PG_VF
 }
 int pg_launch_vol_vertex(hipStream_t s, const GParams &g, const SceneDev &sc, const VolDev &v, const SDDev &sd,
                          const VolWave &w, Queue med, uint32_t max_med, Queue surf, uint32_t max_surf, Queue dsurf,
@@ -1473,8 +1577,9 @@ int pg_launch_vol_vertex(hipStream_t s, const GParams &g, const SceneDev &sc, co
     const char *se = std::getenv("PG_VOL_SPLIT_VERTEX");
     const bool split = se && *se ? std::atoi(se) != 0 : true;
 #define PG_VV(GU, NS, KIND, ROWS, MB)                                                                                \
-    hipLaunchKernelGGL((k_vvertex<GU, NS, KIND, DE>), dim3(PG_QSHARDS * (ROWS)), dim3(TRACE_BLOCK), 0, s, g, sc, v, sd, w, \
-                       med, surf, dsurf, MB, PG_QSHARDS * dr, next_flight, next_surf, next_dsurf, qn)
+    hipLaunchKernelGGL((k_vvertex<GU, NS, KIND, DE, (HO && !(NS && (KIND == 1 || KIND == 3)))>),                       \
+                       dim3(PG_QSHARDS * (ROWS)), dim3(TRACE_BLOCK), 0, s, g, sc, v, sd, w, med, surf, dsurf, MB,        \
+                       PG_QSHARDS * dr, next_flight, next_surf, next_dsurf, qn)
 #define PG_VV_ALL(GU, NS)                                                                                            \
     if (!split) {                                                                                                    \
         PG_VV(GU, NS, 2, mr + dr + sr, PG_QSHARDS * mr);                                                             \
@@ -1484,16 +1589,23 @@ int pg_launch_vol_vertex(hipStream_t s, const GParams &g, const SceneDev &sc, co
         else if (dr + sr) PG_VV(GU, NS, 1, dr + sr, 0u);                                                             \
     }
     // sc.delta: delta emitters are set (pg_set_delta_emitters); scenes without them launch the kernels they always did
-    auto launch = [&](auto de) {
-        constexpr bool DE = decltype(de)::value;
+    // v.homog: homogeneous media are set (pg_set_homogeneous_media), likewise; the surface launches of the k_vnee
+    // stage walk no medium, so they stay the instantiations they were
+    auto launch = [&](auto de, auto ho) {
+        constexpr bool DE = decltype(de)::value, HO = decltype(ho)::value;
         if (g.guiding) {
             if (nee) { PG_VV_ALL(true, true) } else { PG_VV_ALL(true, false) }
         } else {
             if (nee) { PG_VV_ALL(false, true) } else { PG_VV_ALL(false, false) }
         }
     };
-    if (sc.delta) launch(std::true_type{});
-    else launch(std::false_type{});
+    if (v.homog) {
+        if (sc.delta) launch(std::true_type{}, std::true_type{});
+        else launch(std::false_type{}, std::true_type{});
+    } else {
+        if (sc.delta) launch(std::true_type{}, std::false_type{});
+        else launch(std::false_type{}, std::false_type{});
+    }
 #undef PG_VV_ALL
 #undef PG_VV
     return split ? (mr ? 1 : 0) + (dr + sr ? 1 : 0) : 1;  // kernels launched (bench.py's per-launch averages)
@@ -1502,10 +1614,13 @@ void pg_launch_vol_nee(hipStream_t s, const GParams &g, const SceneDev &sc, cons
                        uint32_t max_nee) {
     if (!max_nee) return;
     const dim3 grid(PG_QSHARDS * vrows(max_nee, TRACE_MAX_BLOCKS / PG_QSHARDS));
-    if (g.guiding)
-        hipLaunchKernelGGL(k_vnee<true>, grid, dim3(TRACE_BLOCK), 0, s, g, sc, v, w, nee);
-    else
-        hipLaunchKernelGGL(k_vnee<false>, grid, dim3(TRACE_BLOCK), 0, s, g, sc, v, w, nee);
+#define PG_VN(GU, HO) hipLaunchKernelGGL((k_vnee<GU, HO>), grid, dim3(TRACE_BLOCK), 0, s, g, sc, v, w, nee)
+    if (v.homog) {  // homogeneous media are set: the walks' transmittances are chromatic
+        if (g.guiding) PG_VN(true, true); else PG_VN(false, true);
+    } else {
+        if (g.guiding) PG_VN(true, false); else PG_VN(false, false);
+    }
+#undef PG_VN
 }
 void pg_launch_vol_tail(hipStream_t s, const GParams &g, const SceneDev &sc, const VolDev &v, const SDDev &sd,
                         const VolWave &w, Queue flight, uint32_t max_flight, Queue surf, uint32_t max_surf, Queue dsurf,
@@ -1517,25 +1632,31 @@ void pg_launch_vol_tail(hipStream_t s, const GParams &g, const SceneDev &sc, con
     if (fr + sr + dr == 0) return;
     const dim3 grid(PG_QSHARDS * (fr + dr + sr));
 #define PG_VT(GU, MO)                                                                                                \
-    hipLaunchKernelGGL((k_vtail<GU, MO, DE>), grid, dim3(TRACE_BLOCK), 0, s, g, sc, v, sd, w, flight, surf, dsurf,      \
+    hipLaunchKernelGGL((k_vtail<GU, MO, DE, HO>), grid, dim3(TRACE_BLOCK), 0, s, g, sc, v, sd, w, flight, surf, dsurf,      \
                        PG_QSHARDS * fr, PG_QSHARDS * dr)
-    auto launch = [&](auto de) {  // sc.delta: the instantiations with the delta emitters' NEE compiled in
-        constexpr bool DE = decltype(de)::value;
+    // sc.delta: the instantiations with the delta emitters' NEE compiled in; v.homog: with the homogeneous media
+    auto launch = [&](auto de, auto ho) {
+        constexpr bool DE = decltype(de)::value, HO = decltype(ho)::value;
         if (g.guiding) {
             if (v.models) PG_VT(true, PG_MODELS_DIFFUSE_NULL); else PG_VT(true, -1);
         } else {
             if (v.models) PG_VT(false, PG_MODELS_DIFFUSE_NULL); else PG_VT(false, -1);
         }
     };
-    if (sc.delta) launch(std::true_type{});
-    else launch(std::false_type{});
+    if (v.homog) {
+        if (sc.delta) launch(std::true_type{}, std::true_type{});
+        else launch(std::false_type{}, std::true_type{});
+    } else {
+        if (sc.delta) launch(std::true_type{}, std::false_type{});
+        else launch(std::false_type{}, std::false_type{});
+    }
 #undef PG_VT
 }
 
 namespace {
 }  // namespace
 
-template <bool GUIDED, bool LENS, bool DELTA = false>
+template <bool GUIDED, bool LENS, bool DELTA = false, bool HOMOG = false>
 __global__ __launch_bounds__(VOL_BLOCK, PG_VOL_WAVES) void k_volpath(GParams g, SceneDev sc, VolDev v, SDDev sd,
                                                        const uint32_t *__restrict__ local_pixels, uint32_t pix_begin,
                                                        uint32_t npix, uint32_t nlayers, uint32_t sample_base) {
@@ -1569,7 +1690,7 @@ __global__ __launch_bounds__(VOL_BLOCK, PG_VOL_WAVES) void k_volpath(GParams g, 
             }
         }
         if (!__any(alive)) break;
-        if (alive && !volStepResolved<GUIDED, -1, DELTA>(g, sc, v, sd, P, rng, stk, item, segs, shadows)) {
+        if (alive && !volStepResolved<GUIDED, -1, DELTA, HOMOG>(g, sc, v, sd, P, rng, stk, item, segs, shadows)) {
 #if PG_VOL_CHECK
             if (VCHK(item < nitems, 3, item))
 #endif
@@ -1679,6 +1800,40 @@ __global__ __launch_bounds__(256) void k_medium_query(const GMedium *medium, int
     }
 }
 
+// pg_homogeneous_query: the integrator's homogSampleDistance (op 0) / homogTransmittance (op 1) on given rays
+__global__ __launch_bounds__(256) void k_homog_query(const GMedium *medium, int op, const float *in, const uint32_t *keys,
+                                                     uint32_t n, float *out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *r = in + 8 * (size_t)i;
+    float *q = out + 8 * (size_t)i;
+    const f3 o = mk(r[0], r[1], r[2]), d = mk(r[4], r[5], r[6]);
+    if (op == 0) {
+        VRng rng{keys[2 * i], keys[2 * i + 1], 1, 0};
+        HomSample s;
+        const bool ok = homogSampleDistance(*medium, o, d, r[3], r[7], rng, s);
+        q[0] = ok ? 1.0f : 0.0f;
+        q[1] = s.t;
+        q[2] = s.tr.x;
+        q[3] = s.tr.y;
+        q[4] = s.tr.z;
+        q[5] = s.pdfSuccess;
+        q[6] = s.pdfFailure;
+        q[7] = (float)(rng.dim - 1);
+    } else {
+        const f3 tr = homogTransmittance(*medium, r[3], r[7]);
+        q[0] = tr.x;
+        q[1] = tr.y;
+        q[2] = tr.z;
+        q[3] = q[4] = q[5] = q[6] = q[7] = 0.0f;
+    }
+}
+void pg_launch_homog_query(hipStream_t s, const GMedium *medium, int op, const float *in, const uint32_t *keys,
+                           uint32_t n, float *out) {
+    if (!n) return;
+    hipLaunchKernelGGL(k_homog_query, dim3((n + 255) / 256), dim3(256), 0, s, medium, op, in, keys, n, out);
+}
+
 void pg_launch_phase_query(hipStream_t s, const GMedium *medium, const float *in, const float *wog, uint32_t n,
                            float *out) {
     if (!n) return;
@@ -1699,17 +1854,23 @@ void pg_launch_volpath(hipStream_t s, const GParams &g, const SceneDev &sc, cons
     const uint64_t want = (n + VOL_BLOCK - 1) / VOL_BLOCK;
     const uint32_t grid = (uint32_t)(want < TRACE_MAX_BLOCKS ? want : TRACE_MAX_BLOCKS);
 #define PG_VP(G, L)                                                                                              \
-    hipLaunchKernelGGL((k_volpath<G, L, DE>), dim3(grid), dim3(VOL_BLOCK), 0, s, g, sc, v, sd, local_pixels, pix_begin, \
+    hipLaunchKernelGGL((k_volpath<G, L, DE, HO>), dim3(grid), dim3(VOL_BLOCK), 0, s, g, sc, v, sd, local_pixels, pix_begin, \
                        npix, nlayers, sample_base)
-    auto launch = [&](auto de) {  // sc.delta: the instantiations with the delta emitters' NEE compiled in
-        constexpr bool DE = decltype(de)::value;
+    // sc.delta: the instantiations with the delta emitters' NEE compiled in; v.homog: with the homogeneous media
+    auto launch = [&](auto de, auto ho) {
+        constexpr bool DE = decltype(de)::value, HO = decltype(ho)::value;
         if (g.lens_radius > 0) {  // a thin lens (pg_set_lens); off: the kernels as they were
             if (g.guiding) PG_VP(true, true); else PG_VP(false, true);
         } else {
             if (g.guiding) PG_VP(true, false); else PG_VP(false, false);
         }
     };
-    if (sc.delta) launch(std::true_type{});
-    else launch(std::false_type{});
+    if (v.homog) {
+        if (sc.delta) launch(std::true_type{}, std::true_type{});
+        else launch(std::false_type{}, std::true_type{});
+    } else {
+        if (sc.delta) launch(std::true_type{}, std::false_type{});
+        else launch(std::false_type{}, std::false_type{});
+    }
 #undef PG_VP
 }

@@ -126,6 +126,32 @@ class Device:
             self.set_lens(*scene.lens)
         if getattr(scene, "delta_emitters", None):  # pg_upload_scene cleared any delta emitters of an earlier scene
             self.set_delta_emitters(scene.delta_emitters)
+        if getattr(scene, "homogeneous_media", None):  # pg_upload_scene cleared any records of an earlier scene
+            self.set_homogeneous_media(scene.homogeneous_media)
+
+    def set_homogeneous_media(self, media):
+        """pg_set_homogeneous_media: pg_homogeneous_medium records (Scene.add_homogeneous_medium), each replacing the
+        entry of the uploaded scene's media it names.  Volumetric integrator; after upload, before the first render
+        pass; an empty list removes them."""
+        media = list(media)
+        arr = (capi.pg_homogeneous_medium * max(1, len(media)))(*media)
+        self._chk(self.lib.pg_set_homogeneous_media(self.h, arr, len(media)))
+
+    def homogeneous_query(self, medium, rays, keys=None, transmittance=False):
+        """pg_homogeneous_query on the homogeneous medium `medium`: rays n x 8 (o, mint, d, maxt); keys n x 2 u32 (rng
+        key, sample).  sampleDistance -> n x 8 (success, t, transmittance rgb, pdfSuccess, pdfFailure, draws used);
+        transmittance=True: evalTransmittance -> n x 8 (rgb, zeros)."""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        if keys is None and not transmittance:
+            raise ValueError("homogeneous_query: sampleDistance needs keys")
+        if keys is not None:
+            keys = np.ascontiguousarray(keys, np.uint32).reshape(-1, 2)
+            if len(keys) != len(rays):
+                raise ValueError("homogeneous_query: one key pair per ray")
+        out = np.zeros((len(rays), 8), np.float32)
+        self._chk(self.lib.pg_homogeneous_query(self.h, int(medium), 1 if transmittance else 0, _p(rays),
+                                                None if keys is None else _p(keys), len(rays), _p(out)))
+        return out
 
     def set_delta_emitters(self, emitters):
         """pg_set_delta_emitters: point, spot and directional lights (pg_delta_emitter records, scenes.point_light /

@@ -31,8 +31,10 @@ adapter's flatten() produces from Scene::getShapes()/getBSDFs() (INTEGRATION.md)
                     (as a uniform envmap); point (position or toWorld), spot (toWorld, cutoffAngle, beamWidth;
                     no projection texture) and directional (direction or toWorld), each with its intensity /
                     irradiance given and samplingWeight 1, recorded as Scene.delta_emitters
-  medium            homogeneous (sigmaS / sigmaA or sigmaT / albedo, scale, g; grey sigmaT) with an hg or
-                    isotropic phase, declared at the top level or nested in a shape, attached to
+  medium            homogeneous (sigmaS / sigmaA or sigmaT / albedo, scale, g, mediumSamplingWeight, strategy
+                    balance) with an hg or isotropic phase: a chromatic sigmaT (or any, with
+                    load(analytic_media=True)) becomes a Scene.homogeneous_media record, a grey one a constant
+                    grid; declared at the top level or nested in a shape, attached to
                     shapes as <ref name="interior|exterior">; a shape without a BSDF is a null
                     (index-matched) surface when it is a medium transition, black diffuse when it is
                     an emitter, 0.5 diffuse otherwise (Shape::configure, shape.cpp:48-72)
@@ -113,7 +115,10 @@ class _Loader:
         self.strict = strict
         self.sphere_res = sphere_res
         self.ids = {}
-        self.media = []  # homogeneous media in declaration order: (sigma_t, albedo rgb, g); built in finish()
+        # homogeneous media in declaration order, built in finish(): (sigma_t, albedo rgb, g) for a grey one flattened
+        # into a grid, (sigma_a rgb, sigma_s rgb, g, mediumSamplingWeight) for an analytic one
+        self.media = []
+        self.analytic_media = False  # load(analytic_media=True): grey media take the analytic path too
         self.out = XMLScene()
         self.sc = scenes.Scene()
         # the film's reconstruction filter (name, stddev); Film::Film's default when the scene names none
@@ -488,9 +493,11 @@ class _Loader:
         scale = float(P.get("scale", 1.0))
         ss, sa = ss * (1 - g_red) * scale, sa * scale  # Medium::Medium reduced scattering, then lookupMaterial scale
         st = ss + sa
-        if not np.allclose(st, st[0], rtol=1e-6):
-            raise NotImplementedError("<medium>: chromatic sigmaT (the GPU medium has one extinction per point)")
-        if not st[0] > 0:
+        strategy = P.get("strategy", "balance")
+        if strategy != "balance":  # homogeneous.cpp:190-226
+            raise NotImplementedError(f"<medium>: strategy=\"{strategy}\" (only balance is restated)")
+        analytic = self.analytic_media or not np.allclose(st, st[0], rtol=1e-6)
+        if not (st.max() > 0 if analytic else st[0] > 0):
             raise ValueError("<medium>: sigmaT must be > 0")
         g = 0.0
         for c in el:
@@ -500,7 +507,10 @@ class _Loader:
                     g = float(self.props(c).get("g", 0.8))  # hg.cpp:50
                 elif pt != "isotropic":
                     raise NotImplementedError(f"<phase type=\"{pt}\"> (hg and isotropic only)")
-        self.media.append((float(st[0]), tuple((ss / st).tolist()), g))
+        if analytic:
+            self.media.append((sa.tolist(), ss.tolist(), g, float(P.get("mediumSamplingWeight", -1.0))))
+        else:  # a grid has no medium sampling weight: load(analytic_media=True) honours it
+            self.media.append((float(st[0]), tuple((ss / st).tolist()), g))
         idx = len(self.media) - 1
         if el.get("id"):
             self.ids[el.get("id")] = ("medium", idx)
@@ -515,7 +525,11 @@ class _Loader:
         P = np.concatenate(self.sc._pos)
         lo, hi = P.min(0), P.max(0)
         ext = float((hi - lo).max()) + 1e-3
-        for st, alb, g in self.media:
+        for m in self.media:
+            if len(m) == 4:  # analytic: Scene.homogeneous_media
+                self.sc.add_homogeneous_medium(sigma_a=m[0], sigma_s=m[1], g=m[2], medium_sampling_weight=m[3])
+                continue
+            st, alb, g = m
             self.sc.add_medium(np.ones((2, 2, 2), np.float32), tuple((lo - ext).tolist()), tuple((hi + ext).tolist()),
                                st, alb, g)
 
@@ -663,10 +677,11 @@ class _Loader:
         return self.out
 
 
-def load(source, defines=None, strict=True, sphere_res=(64, 32)):
+def load(source, defines=None, strict=True, sphere_res=(64, 32), analytic_media=False):
     """Parse a Mitsuba 0.5 scene (a path, or the XML text itself) into an XMLScene.  `defines` are the
     -D key=value substitutions (mitsuba.cpp:154).  The Scene is finalized when it has shapes and a
-    camera (BSDF-only files such as data/tests/test_bsdf.xml return scene = None)."""
+    camera (BSDF-only files such as data/tests/test_bsdf.xml return scene = None).  analytic_media: grey
+    homogeneous media become Scene.homogeneous_media records too (chromatic ones always do) instead of grids."""
     if os.path.exists(str(source)):
         root = ET.parse(source).getroot()
         base = os.path.dirname(os.path.abspath(source))
@@ -674,6 +689,7 @@ def load(source, defines=None, strict=True, sphere_res=(64, 32)):
         root = ET.fromstring(source)
         base = os.getcwd()
     L = _Loader(base, defines or {}, strict, sphere_res)
+    L.analytic_media = bool(analytic_media)
     out = L.run(root)
     L.finish_media()
     if L.sc.shapes and L.sc.camera is not None:
@@ -1127,7 +1143,9 @@ def _delta_emitter_xml(e):
 def save(scene, path, spp=64, integrator="path"):
     """Write `scene` as a Mitsuba 0.5 scene: one OBJ per shape (positions, normals), inline BSDFs,
     area emitters, the perspective sensor (lookat + fov along x; thinlens with apertureRadius and focusDistance
-    when the scene has a lens), a box-filtered hdrfilm, and the environment map as a PFM.  load(path) reads it back to the same arrays."""
+    when the scene has a lens), a box-filtered hdrfilm, and the environment map as a PFM.  The scene's homogeneous
+    media (Scene.homogeneous_media) are written as <medium type="homogeneous"> with an hg phase, referenced by their
+    shapes; grid media are not written.  load(path) reads it back to the same arrays."""
     d = os.path.dirname(os.path.abspath(path))
     stem = os.path.splitext(os.path.basename(path))[0]
     os.makedirs(d, exist_ok=True)
@@ -1149,6 +1167,13 @@ def save(scene, path, spp=64, integrator="path"):
                f'<sampler type="independent"><integer name="sampleCount" value="{int(spp)}"/></sampler>'
                f'<film type="hdrfilm"><integer name="width" value="{cam.width}"/><integer name="height" '
                f'value="{cam.height}"/><rfilter type="box"/></film></sensor>')
+    homog = {int(h.medium): f"medium{int(h.medium)}" for h in getattr(sc, "homogeneous_media", [])}
+    for h in getattr(sc, "homogeneous_media", []):
+        w = float(np.float32(h.medium_sampling_weight))
+        wxml = "" if w == -1.0 else f'<float name="mediumSamplingWeight" value="{w!r}"/>'
+        out.append(f'<medium type="homogeneous" id="{homog[int(h.medium)]}">{_rgb_el("sigmaA", f32l(h.sigma_a))}'
+                   f'{_rgb_el("sigmaS", f32l(h.sigma_s))}{wxml}'
+                   f'<phase type="hg"><float name="g" value="{float(np.float32(h.g))!r}"/></phase></medium>')
     UV = sc.texcoords
     bound = dict(sc.texture_bindings)
     tex_files = {}
@@ -1188,8 +1213,10 @@ def save(scene, path, spp=64, integrator="path"):
             slot = "reflectance" if m.type == capi.PG_BSDF_DIFFUSE else "diffuseReflectance"
             tex = _texture_xml(sc.textures[bound[sh.material]], slot, tex_files.get(bound[sh.material]))
         flip = '<boolean name="flipTexCoords" value="false"/>' if UV is not None else ""
+        med = "".join(f'<ref name="{side}" id="{homog[m]}"/>'
+                      for side, m in (("interior", sh.interior_medium), ("exterior", sh.exterior_medium)) if m in homog)
         out.append(f'<shape type="obj"><string name="filename" value="{fn}"/>{flip}'
-                   f'{_bsdf_xml(sc.materials[sh.material], tex)}{em}</shape>')
+                   f'{_bsdf_xml(sc.materials[sh.material], tex)}{em}{med}</shape>')
     if sc.envmap is not None:
         fn = f"{stem}_envmap.pfm"
         img = np.ascontiguousarray(sc._env_rgb[::-1], "<f4")

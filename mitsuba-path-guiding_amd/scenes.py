@@ -102,6 +102,9 @@ class Scene:
         self.lens = None
         # delta emitters (pg_set_delta_emitters): pg_delta_emitter records, picked after the area emitters
         self.delta_emitters = []
+        # homogeneous media (pg_set_homogeneous_media): pg_homogeneous_medium records, each replacing a placeholder
+        # entry of `media`
+        self.homogeneous_media = []
 
     # -- construction
     def add_material(self, m):
@@ -125,6 +128,35 @@ class Scene:
         self._densities.append(dens)
         self.media.append(m)
         return len(self.media) - 1
+
+    def add_homogeneous_medium(self, sigma_a=None, sigma_s=None, sigma_t=None, albedo=None, g=0.0,
+                               medium_sampling_weight=-1.0):
+        """Homogeneous medium (src/medium/homogeneous.cpp, strategy = balance): RGB sigma_a and sigma_s, or sigma_t and
+        albedo (either pair, never a mix: materials.h:104-106; a missing member of the pair is 0 for the coefficients
+        and 1 for sigma_t / albedo), HG phase g, medium sampling weight (-1: the reference's default rule).  Returns
+        a medium index usable as `interior`, `exterior` or `camera_medium`: a placeholder pg_medium (a 2^3 grid of
+        ones) that Device.upload replaces by the record in `homogeneous_media` (pg_set_homogeneous_media)."""
+        has_as, has_ta = sigma_a is not None or sigma_s is not None, sigma_t is not None or albedo is not None
+        if has_as and has_ta:
+            raise ValueError("add_homogeneous_medium: sigma_s & sigma_a *or* sigma_t & albedo (materials.h:104-106)")
+        if not has_as and not has_ta:
+            raise ValueError("add_homogeneous_medium: no coefficients given")
+        rgb = lambda v, d: np.broadcast_to(np.asarray(d if v is None else v, np.float32), (3,)).copy()
+        if has_ta:
+            st, alb = rgb(sigma_t, 1.0), rgb(albedo, 1.0)
+            ss = alb * st
+            sa = st - ss
+        else:
+            sa, ss = rgb(sigma_a, 0.0), rgb(sigma_s, 0.0)
+        idx = self.add_medium(np.ones((2, 2, 2), np.float32), (0.0, 0.0, 0.0), (1.0, 1.0, 1.0), 1.0, (0.0, 0.0, 0.0), g)
+        h = capi.pg_homogeneous_medium()
+        h.medium = idx
+        h.sigma_a = (C.c_float * 3)(*sa.tolist())
+        h.sigma_s = (C.c_float * 3)(*ss.tolist())
+        h.g = g
+        h.medium_sampling_weight = medium_sampling_weight
+        self.homogeneous_media.append(h)
+        return idx
 
     def add_mesh(self, V, F, N=None, material=0, radiance=None, interior=-1, exterior=-1, uv=None):
         """`uv`: per-vertex texture coordinates (len(V), 2), or None (a textured material then sees the hit's

@@ -132,6 +132,8 @@ public:
         // point, spot and directional emitters (flattenDeltaEmitters); after the upload, before any pass
         if (!m_flat.deltas.empty())
             check(pg_set_delta_emitters(m_ctx, m_flat.deltas.data(), (uint32_t) m_flat.deltas.size()));
+        if (!m_flat.homogeneous.empty())
+            check(pg_set_homogeneous_media(m_ctx, m_flat.homogeneous.data(), (uint32_t) m_flat.homogeneous.size()));
         // the film's reconstruction filter: any separable filter through its own discretised table
         // (rfilter.h:76-77); the box keeps the per-pixel film
         const ReconstructionFilter *rf = scene->getSensor()->getFilm()->getReconstructionFilter();
@@ -409,6 +411,7 @@ protected:
         bool mirrorX = false, hasEnv = false;
         float lensRadius = 0, focusDistance = 0;  // the thinlens sensor (pg_set_lens); radius 0: a pinhole
         std::vector<pg_delta_emitter> deltas;     // point, spot and directional emitters (pg_set_delta_emitters)
+        std::vector<pg_homogeneous_medium> homogeneous;  // homogeneous media (pg_set_homogeneous_media)
         void bind() {  // pg_upload_scene copies everything; the arrays live until then
             desc.num_vertices = (uint32_t) (pos.size() / 3);
             desc.num_triangles = (uint32_t) (idx.size() / 3);
@@ -690,7 +693,9 @@ inline void GuidedGPUIntegrator::flattenEnvironment(const Scene *scene, Flattene
 
 // A participating medium -> pg_medium (index into f.media, memoised).  pg_medium is a density grid
 // in [0, 1] times `scale` over an AABB with a constant albedo and an HG phase function:
-//   homogeneous (isHomogeneous): a constant 2^3 grid over the scene bounds, scale = sigma_t (grey);
+//   homogeneous (isHomogeneous): a pg_homogeneous_medium record (getSigmaA / getSigmaS, medium.h:163-169, the
+//     plugin's mediumSamplingWeight; strategy balance only) that replaces a placeholder entry, a constant 2^3 grid
+//     over the scene bounds: the library then samples it as homogeneous.cpp does, chromatic sigma_t included;
 //   heterogeneous (HeterogeneousMedium): the fork's per-point queries (medium.h:168-190,
 //     getSigmaT(p) / getScale() = the density, getAlbedo(p)) sampled at the nodes of a
 //     mediumResolution^3 grid over the AABB of the medium's boundary shapes -- exact for a
@@ -712,16 +717,30 @@ inline int32_t GuidedGPUIntegrator::flattenMedium(const Medium *med, const AABB 
     else if (pcls == "IsotropicPhaseFunction") pm.g = 0.0f;
     else Log(EError, "guided_gpu: phase function %s is not supported (hg, isotropic)", pcls.c_str());
     if (med->isHomogeneous()) {
-        const Spectrum st = med->getSigmaT(), alb = med->getAlbedo();
-        if (st.max() != st.min()) Log(EError, "guided_gpu: chromatic sigmaT is not supported");
+        const Spectrum st = med->getSigmaT();
+        const std::string strategy = med->getProperties().getString("strategy", "balance");
+        if (strategy != "balance")
+            Log(EError, "guided_gpu: homogeneous medium strategy \"%s\" is not supported (balance)", strategy.c_str());
+        if (!(st.max() > 0)) Log(EError, "guided_gpu: a homogeneous medium needs sigmaT > 0 in some channel");
+        pg_homogeneous_medium hm;
+        memset(&hm, 0, sizeof(hm));
+        hm.medium = (uint32_t) f.media.size();
+        float rgb[4];  // pgRGB writes four floats
+        pgRGB(med->getSigmaA(), rgb);
+        for (int a = 0; a < 3; ++a) hm.sigma_a[a] = rgb[a];
+        pgRGB(med->getSigmaS(), rgb);
+        for (int a = 0; a < 3; ++a) hm.sigma_s[a] = rgb[a];
+        hm.g = pm.g;
+        hm.medium_sampling_weight = (float) med->getProperties().getFloat("mediumSamplingWeight", -1.0f);
+        f.homogeneous.push_back(hm);
         for (int a = 0; a < 3; ++a) {
             pm.aabb_min[a] = (float) (bounds.min[a] - bounds.getExtents()[a]);
             pm.aabb_max[a] = (float) (bounds.max[a] + bounds.getExtents()[a]);
         }
         pm.res[0] = pm.res[1] = pm.res[2] = 2;
         dens.assign(8, 1.0f);
-        pm.scale = (float) st[0];
-        pgRGB(alb, pm.albedo);
+        pm.scale = (float) st.max();  // the placeholder entry: not read once the record is set
+        pm.albedo[0] = pm.albedo[1] = pm.albedo[2] = 0.0f;
     } else {
         const int R = m_mediumResolution;
         const Float scale = med->getScale();
@@ -743,7 +762,9 @@ inline int32_t GuidedGPUIntegrator::flattenMedium(const Medium *med, const AABB 
             if (!(med->getAlbedo(bounds.getCorner(k)) == alb) && med->getSigmaT(bounds.getCorner(k)).max() > 0)
                 Log(EError, "guided_gpu: spatially varying albedo is not supported");
         pm.scale = (float) scale;
-        pgRGB(alb, pm.albedo);
+        float rgb[4];  // pgRGB writes four floats: pm.albedo has three, and g follows it
+        pgRGB(alb, rgb);
+        for (int a = 0; a < 3; ++a) pm.albedo[a] = rgb[a];
     }
     f.densities.push_back(dens);
     f.media.push_back(pm);

@@ -1,6 +1,7 @@
 // src/integrators/path/guided_gpu_volpath.cpp -- the volumetric plugin: SD-tree guided progressive
 // volumetric path tracer on the MI355X (ProgressiveVolumetricPathTracer's surface,
-// progressive_volpath.cpp:71-470: homogeneous and heterogeneous media flattened to pg_medium, HG phase,
+// progressive_volpath.cpp:71-470: heterogeneous media flattened to pg_medium, homogeneous media (chromatic sigmaT,
+// mediumSamplingWeight; strategy balance) to pg_homogeneous_medium records, HG phase,
 // null-BSDF medium transitions; guided distance sampling with `distanceGuiding`), over the pg C-ABI.
 #include "guided_gpu.h"
 
