@@ -593,6 +593,18 @@ pg_status pg_get_shadow_culled(void *ctx, uint64_t *count);
 /* The current blocker list: *count (<= 8) BVH-order triangle ids in tri_ids[8], most frequent first, and (orig_ids
  * not NULL) the same triangles' indices in the uploaded scene. */
 pg_status pg_get_blockers(void *ctx, uint32_t *tri_ids, uint32_t *orig_ids, uint32_t *count);
+/* Path integrator: doom probes since create (each counted in pg_get_probes, and in pg_get_culled as the hit it is)
+ * that the tracing kernels answered against the learned occluder list instead of walking the tree.  The probe rows of
+ * the recording passes count, per triangle, the probes whose walk ended on it; after each of them up to 16 triangles
+ * that each took at least 1/64 of the counted probes are listed (kept only if together they took half), and a later
+ * probe that certainly hits one of them anywhere along its ray (the blocker test's margins, so the walk would return
+ * a hit too) skips its walk.  No counter or result depends on the list.  0 with PG_NO_PROBE_LIST=1 in the
+ * environment, before the first recording pass, after pg_upload_scene / pg_put_sdtree (the list is emptied),
+ * wherever pg_get_probes is 0, and for the probes of a chunk's tail launch (they always walk).  A read-only entry
+ * point like pg_get_culled: pg_stats keeps its ABI 12 layout. */
+pg_status pg_get_probes_resolved(void *ctx, uint64_t *count);
+/* The current occluder list, as pg_get_blockers: *count (<= 16) ids in tri_ids[16] and (not NULL) orig_ids[16]. */
+pg_status pg_get_occluders(void *ctx, uint32_t *tri_ids, uint32_t *orig_ids, uint32_t *count);
 /* Number of pixels owned by this rank (tile shard). */
 pg_status pg_local_pixel_count(void *ctx, uint64_t *count);
 
@@ -604,6 +616,11 @@ pg_status pg_trace_rays(void *ctx, const float *rays, uint64_t n, int32_t any_hi
  * triangles tri_ids, installed as the list for this call only: out[i] = 1 where the test answers "certainly
  * occluded", else 0.  Wherever it answers 1, pg_trace_rays(any_hit = 1) answers occluded. */
 pg_status pg_blocker_test(void *ctx, const float *rays, uint64_t n, const uint32_t *tri_ids, uint32_t k, uint32_t *out);
+/* The tracing kernels' occluder test and the probe walk on given rays (n x 8 floats as pg_trace_rays; a probe has no
+ * tmax, the eighth float is ignored) against the k <= 16 BVH-order triangles tri_ids, installed as the list for this
+ * call only: out[2 i] = 1 where the test answers "the walk certainly returns a hit", out[2 i + 1] = 1 where the probe
+ * walk (the any-hit form of the closest-hit walk) returns one.  out[2 i] = 1 implies out[2 i + 1] = 1. */
+pg_status pg_occluder_test(void *ctx, const float *rays, uint64_t n, const uint32_t *tri_ids, uint32_t k, uint32_t *out);
 /* The closest hit's full record as the shading kernels build it (fillIntersectionRecord<true>,
  * skdtree.h:343-430: barycentric position, face normal flipped to the shading normal's side, interpolated
  * shading normal, shading frame by computeShadingFrame(n, dpdu = p1 - p0), wi = toLocal(-d)); the unit KAT of

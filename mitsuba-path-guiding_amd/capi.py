@@ -217,8 +217,11 @@ SIGNATURES = [
     ("pg_get_culled", C.c_int32, [VP, C.POINTER(C.c_uint64)]),
     ("pg_get_probes", C.c_int32, [VP, C.POINTER(C.c_uint64)]),
     ("pg_get_shadow_culled", C.c_int32, [VP, C.POINTER(C.c_uint64)]),
+    ("pg_get_probes_resolved", C.c_int32, [VP, C.POINTER(C.c_uint64)]),
     ("pg_get_blockers", C.c_int32, [VP, VP, VP, C.POINTER(C.c_uint32)]),
     ("pg_blocker_test", C.c_int32, [VP, VP, C.c_uint64, VP, C.c_uint32, VP]),
+    ("pg_get_occluders", C.c_int32, [VP, VP, VP, C.POINTER(C.c_uint32)]),
+    ("pg_occluder_test", C.c_int32, [VP, VP, C.c_uint64, VP, C.c_uint32, VP]),
     ("pg_local_pixel_count", C.c_int32, [VP, C.POINTER(C.c_uint64)]),
     ("pg_trace_rays", C.c_int32, [VP, VP, C.c_uint64, C.c_int32, VP]),
     ("pg_hit_records", C.c_int32, [VP, VP, C.c_uint64, VP]),

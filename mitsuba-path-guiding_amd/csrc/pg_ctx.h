@@ -20,13 +20,16 @@ constexpr uint32_t kMaxBounces = 1100;     // > gpu_depth_cap default (1024) + 2
 // per-bounce device counters (words): [0, 64) shard counts of the live queue entering the bounce,
 // [64, 128) shadow-queue shard counts, [128, 704) shard counts of the PG_NUM_CLASSES material-class
 // queues followed by the escaped-ray and the culled-hit counts (PG_CLASS_ROWS rows), [704, 768) shard counts of the
-// probe queue the bounce's shading fills (pg_layout.h "Doom probe"), [768, 832) the dropped shadow rays
-constexpr uint32_t kBounceWords = 832;
+// probe queue the bounce's shading fills (pg_layout.h "Doom probe"), [768, 832) the dropped shadow rays, [832, 896) the
+// probes of that queue resolved against the occluder list
+constexpr uint32_t kBounceWords = 896;
 constexpr uint32_t kShadowCounts = PG_QSHARDS, kClassCounts = 2 * PG_QSHARDS;
 constexpr uint32_t kProbeCounts = kClassCounts + PG_CLASS_ROWS * PG_QSHARDS;
 // shadow rays the shader resolved against the blocker list (Queue::dropped of the shadow queue)
 constexpr uint32_t kDropCounts = kProbeCounts + PG_QSHARDS;
-static_assert(kDropCounts + PG_QSHARDS <= kBounceWords, "counter layout");
+// probes the tracer resolved against the occluder list (Queue::dropped of the probe queue; pg_layout.h "Probe occluders")
+constexpr uint32_t kResolvedCounts = kDropCounts + PG_QSHARDS;
+static_assert(kResolvedCounts + PG_QSHARDS <= kBounceWords, "counter layout");
 constexpr uint32_t kCounterWords = kBounceWords * (kMaxBounces + 1);
 constexpr size_t kTailStats = 6;  // k_tail: segments, escaped, shadow rays, culled, probes, blocker-resolved shadow rays
 
@@ -178,6 +181,12 @@ struct Ctx {
     PinnedBuf h_blk_counts;     // the counts' host copy (learnBlockers)
     std::vector<float> host_tris, host_shade;  // host copies of tris and tshade: the listed triangles' records
     bool blk_stopped = false;   // no more counting in this job, the list stays (learnBlockers)
+    // probe occluders (pg_layout.h "Probe occluders"): counted in the second half of blk_counts (num_tris + 1 words
+    // each, one readback for both), learned and reset with the blockers
+    bool prb_stopped = false;
+    uint32_t num_occluders = 0;
+    uint32_t prb_ids[PG_PROBE_LIST_MAX] = {}, prb_orig[PG_PROBE_LIST_MAX] = {};
+    float prb[PG_PROBE_LIST_MAX][12] = {};
     uint32_t num_blockers = 0;
     uint32_t blk_ids[PG_MAX_BLOCKERS] = {}, blk_orig[PG_MAX_BLOCKERS] = {};  // BVH-order and original ids
     float blk[PG_MAX_BLOCKERS][12] = {};
@@ -251,6 +260,7 @@ struct Ctx {
     pg_stats stats{};
     uint64_t culled = 0;  // segments whose hit the tracer culled (pg_get_culled); counted in stats.segments
     uint64_t probes = 0;  // segments answered by an any-hit probe (pg_get_probes); counted in culled or escaped
+    uint64_t probes_resolved = 0;  // probes answered by the occluder list without a walk (pg_get_probes_resolved); counted in probes
     uint64_t shadow_culled = 0;  // shadow rays resolved against the blocker list; counted in stats.shadow_rays
 };
 
@@ -272,7 +282,8 @@ PathDev pathView(const Lane *l);
 pg_status ensurePaths(Ctx *c, uint32_t want, bool rec);
 void releasePaths(Ctx *c);
 pg_status ensureRecords(Ctx *c, uint64_t want);
-pg_status learnBlockers(Ctx *c);
+pg_status learnBlockers(Ctx *c, bool blockers, bool occluders);
+bool probeListEnabled(const Ctx *c);
 void launchFilmFiltered(Ctx *c, hipStream_t s, const GParams &g, const SceneDev &sc, const PathDev &p,
                         const uint32_t *pixels, uint32_t pb, uint32_t np, uint32_t nl, uint32_t sample_base);
 int vertexSlots(const Ctx *c, bool rec);

@@ -177,6 +177,8 @@ pg_status upload(Ctx *c, DevBuf &b, const std::vector<T> &v) {
     return PG_OK;
 }
 
+// the one reader of the occluder list's switch (read per call: the tests flip it between jobs of one process)
+bool probeListEnabled(const Ctx *c) { return !c->has_env && !std::getenv("PG_NO_PROBE_LIST"); }
 SceneDev sceneView(const Ctx *c) {
     SceneDev sc{c->nodes.as<float4>(), c->tris.as<float4>(), c->wnodes.as<float4>(), c->tris.as<float4>(),
                 c->tshade.as<float4>(), c->tclass.as<uint8_t>(),
@@ -191,6 +193,10 @@ SceneDev sceneView(const Ctx *c) {
     sc.absmax = c->absmax;
     sc.blk_counts = sc.blk_total = nullptr;  // set by the recording passes
     std::memcpy(sc.blk, c->blk, sizeof(sc.blk));
+    // the occluder list; PG_NO_PROBE_LIST=1 (or an environment emitter: no probes) renders with an empty one
+    sc.num_occluders = probeListEnabled(c) ? c->num_occluders : 0u;
+    sc.prb_counts = sc.prb_total = nullptr;  // set by the recording passes
+    std::memcpy(sc.prb, c->prb, sizeof(sc.prb));
     if (c->textured) {
         sc.tuv = c->tuv.as<float4>();
         sc.tex = c->tex.as<GTex>();
@@ -200,20 +206,21 @@ SceneDev sceneView(const Ctx *c) {
     return sc;
 }
 
-// a new job on the scene: no blockers, no counts
+// a new job on the scene: no blockers, no probe occluders, no counts
 pg_status resetBlockers(Ctx *c) {
-    c->num_blockers = 0;
-    c->blk_stopped = false;
-    if (c->blk_counts.p) HIPC(c, hipMemsetAsync(c->blk_counts.p, 0, ((size_t)c->num_tris + 1) * 4, c->stream));
+    c->num_blockers = c->num_occluders = 0;
+    c->blk_stopped = c->prb_stopped = false;
+    if (c->blk_counts.p) HIPC(c, hipMemsetAsync(c->blk_counts.p, 0, 2 * ((size_t)c->num_tris + 1) * 4, c->stream));
     return PG_OK;
 }
 // lists the triangles `ids` (BVH order) in blk / blk_ids from the host copies of their TriAccel rows and shading
-// records (no device round trip); triangles too small for the test's margins (pg_ray_hits_blockers) are left out
+// records (no device round trip); triangles too small for the test's margins (pg_ray_hits_blockers) are left out.
+// cap: the list's capacity (PG_MAX_BLOCKERS, or PG_PROBE_LIST_MAX for the probe occluders, whose records have the same form)
 pg_status installBlockers(Ctx *c, const uint32_t *ids, uint32_t n, float (*blk)[12], uint32_t *blk_ids, uint32_t *orig,
-                          uint32_t *count) {
+                          uint32_t *count, uint32_t cap = PG_MAX_BLOCKERS) {
     *count = 0;
     uint32_t m = 0;
-    for (uint32_t i = 0; i < n && m < PG_MAX_BLOCKERS; ++i) {
+    for (uint32_t i = 0; i < n && m < cap; ++i) {
         if (ids[i] >= c->num_tris) return fail(c, PG_ERR_INVALID, "blocker triangle id out of range");
         float rows[12];
         for (int r = 0; r < 3; ++r) std::memcpy(rows + 4 * r, &c->host_tris[4 * (size_t)PG_TRI_ROW(ids[i], r)], 16);
@@ -228,12 +235,23 @@ pg_status installBlockers(Ctx *c, const uint32_t *ids, uint32_t n, float (*blk)[
 }
 // after a recording pass: the cumulative counts to the host (pinned; the last word is the number of shadow rays the
 // counts were taken from), the list chosen from them
-pg_status learnBlockers(Ctx *c) {
-    const size_t bytes = ((size_t)c->num_tris + 1) * 4;
+// blockers / occluders: which of the two lists this pass counted for (the other keeps what it has)
+pg_status learnBlockers(Ctx *c, bool blockers, bool occluders) {
+    const size_t bytes = 2 * ((size_t)c->num_tris + 1) * 4;  // both halves in one copy
     HIPC(c, c->h_blk_counts.reserve(bytes));
     const uint32_t *counts = (const uint32_t *)c->h_blk_counts.p;
     HIPC(c, hipMemcpyAsync(c->h_blk_counts.p, c->blk_counts.p, bytes, hipMemcpyDeviceToHost, c->stream));
     HIPC(c, hipStreamSynchronize(c->stream));
+    if (occluders) {  // the same rule and the same stops on the probes' counts (pg_layout.h "Probe occluders")
+        const uint32_t *pc = counts + c->num_tris + 1;
+        uint32_t pids[PG_PROBE_LIST_MAX];
+        const uint32_t ptotal = pc[c->num_tris];
+        const uint32_t pn = pg_select_listed(pc, c->num_tris, ptotal, PG_PROBE_LIST_MAX, pids);
+        if (ptotal >= PG_BLOCKER_COUNT_STOP || (pn == 0 && ptotal >= PG_BLOCKER_DECIDE)) c->prb_stopped = true;
+        if (pg_status s = installBlockers(c, pids, pn, c->prb, c->prb_ids, c->prb_orig, &c->num_occluders, PG_PROBE_LIST_MAX))
+            return s;
+    }
+    if (!blockers) return PG_OK;
     uint32_t ids[PG_MAX_BLOCKERS];
     const uint32_t total = counts[c->num_tris];
     const uint32_t n = pg_select_blockers(counts, c->num_tris, total, ids);
@@ -1346,12 +1364,13 @@ pg_status pg_upload_scene(void *ctx, const pg_scene_desc *d) {
         c->num_em_boxes = pg_emitter_boxes(d->positions, d->indices, triEmitter.data(), nt, d->num_emitters, c->em_box,
                                            &c->em_absmax);
     }
-    c->num_blockers = 0;
-    c->blk_stopped = false;
+    c->num_blockers = c->num_occluders = 0;
+    c->blk_stopped = c->prb_stopped = false;
     c->absmax = 0.0f;
     for (size_t i = 0; i < (size_t)3 * d->num_vertices; ++i) c->absmax = std::max(c->absmax, std::fabs(d->positions[i]));
-    HIPC(c, c->blk_counts.alloc(((size_t)nt + 1) * 4));  // the last word: the shadow rays counted
-    HIPC(c, hipMemsetAsync(c->blk_counts.p, 0, ((size_t)nt + 1) * 4, c->stream));
+    // nt + 1 words for the shadow blockers (the last: the shadow rays counted), then as many for the probe occluders
+    HIPC(c, c->blk_counts.alloc(2 * ((size_t)nt + 1) * 4));
+    HIPC(c, hipMemsetAsync(c->blk_counts.p, 0, 2 * ((size_t)nt + 1) * 4, c->stream));
     c->host_tris = bvh.tris;
     c->host_shade = shade;
     // a new scene has no textures (pg_set_textures)
@@ -1998,6 +2017,22 @@ pg_status pg_get_shadow_culled(void *ctx, uint64_t *count) {
     *count = c->shadow_culled;
     return PG_OK;
 }
+pg_status pg_get_probes_resolved(void *ctx, uint64_t *count) {
+    Ctx *c = (Ctx *)ctx;
+    if (!c || !count) return fail(c, PG_ERR_INVALID, "pg_get_probes_resolved: null argument");
+    *count = c->probes_resolved;
+    return PG_OK;
+}
+pg_status pg_get_occluders(void *ctx, uint32_t *tri_ids, uint32_t *orig_ids, uint32_t *count) {
+    Ctx *c = (Ctx *)ctx;
+    if (!c || !tri_ids || !count) return fail(c, PG_ERR_INVALID, "pg_get_occluders: null argument");
+    *count = c->num_occluders;
+    for (uint32_t i = 0; i < c->num_occluders; ++i) {
+        tri_ids[i] = c->prb_ids[i];
+        if (orig_ids) orig_ids[i] = c->prb_orig[i];
+    }
+    return PG_OK;
+}
 pg_status pg_get_blockers(void *ctx, uint32_t *tri_ids, uint32_t *orig_ids, uint32_t *count) {
     Ctx *c = (Ctx *)ctx;
     if (!c || !tri_ids || !count) return fail(c, PG_ERR_INVALID, "pg_get_blockers: null argument");
@@ -2052,6 +2087,28 @@ pg_status pg_blocker_test(void *ctx, const float *rays, uint64_t n, const uint32
     pg_launch_blocker_test(c->stream, sc, r.as<float>(), (uint32_t)n, o.as<uint32_t>());
     HIPC(c, hipGetLastError());
     HIPC(c, hipMemcpyAsync(out, o.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    return PG_OK;
+}
+
+pg_status pg_occluder_test(void *ctx, const float *rays, uint64_t n, const uint32_t *tri_ids, uint32_t k, uint32_t *out) {
+    Ctx *c = (Ctx *)ctx;
+    if (!c || (!rays && n) || (!out && n) || (!tri_ids && k)) return fail(c, PG_ERR_INVALID, "pg_occluder_test: null argument");
+    if (!c->has_scene) return fail(c, PG_ERR_STATE, "pg_occluder_test: no scene");
+    if (k > PG_PROBE_LIST_MAX) return fail(c, PG_ERR_INVALID, "pg_occluder_test: more than PG_PROBE_LIST_MAX triangles");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    if (!n) return PG_OK;
+    SceneDev sc = sceneView(c);
+    uint32_t ids[PG_PROBE_LIST_MAX];
+    if (pg_status s = installBlockers(c, tri_ids, k, sc.prb, ids, nullptr, &sc.num_occluders, PG_PROBE_LIST_MAX)) return s;
+    DevBuf r, o, ovf;
+    HIPC(c, r.alloc(n * 32));
+    HIPC(c, o.alloc(n * 8));
+    HIPC(c, ovf.alloc(pg_stack_overflow_words(pg_trace_rays_threads(n)) * 4));
+    HIPC(c, hipMemcpyAsync(r.p, rays, n * 32, hipMemcpyHostToDevice, c->stream));
+    pg_launch_occluder_test(c->stream, sc, r.as<float>(), (uint32_t)n, o.as<uint32_t>(), ovf.as<uint32_t>());
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipMemcpyAsync(out, o.p, n * 8, hipMemcpyDeviceToHost, c->stream));
     HIPC(c, hipStreamSynchronize(c->stream));
     return PG_OK;
 }

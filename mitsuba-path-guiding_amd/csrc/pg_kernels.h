@@ -35,6 +35,12 @@ struct SceneDev {
     const uint32_t *mtex;   // per material: the texture bound to its diffuse reflectance, ~0 = none
     // delta emitters (pg_set_delta_emitters): emitters [g.num_area, g.num_area + their count); nullptr while none is set
     const GDelta *delta;
+    // probe occluders (pg_layout.h "Probe occluders"; by value as blk, last so that no other member moves): the listed
+    // records, 0 of them when nothing qualifies, with an environment emitter or with PG_NO_PROBE_LIST=1
+    uint32_t num_occluders;
+    uint32_t *prb_counts;   // per BVH-order triangle: probes whose walk accepted it (recording passes; nullptr: not counted)
+    uint32_t *prb_total;    // the probes, hit or miss, that prb_counts was taken from (one word)
+    float prb[PG_PROBE_LIST_MAX][12];
 };
 
 // float4 per training vertex: (x, woPdf), (T after the vertex, packed canonical wo), (L snapshot, -),
@@ -300,6 +306,9 @@ void pg_launch_texture_query(hipStream_t s, const GTex *tex, const float *uv, ui
 void pg_launch_hit_uvs(hipStream_t s, const SceneDev &sc, const float *rays, uint32_t n, float *out, uint32_t *ovf);
 // unit-level blocker test (pg_blocker_test): out[i] = 1 where pg_ray_hits_blockers answers for ray i against sc.blk
 void pg_launch_blocker_test(hipStream_t s, const SceneDev &sc, const float *rays, uint32_t n, uint32_t *out);
+// unit-level occluder test (pg_occluder_test): out[2 i] = pg_ray_hits_occluders' answer for ray i against sc.prb,
+// out[2 i + 1] = the probe walk's; ovf: pg_stack_overflow_words(pg_trace_rays_threads(n)) words
+void pg_launch_occluder_test(hipStream_t s, const SceneDev &sc, const float *rays, uint32_t n, uint32_t *out, uint32_t *ovf);
 // words of traversal-stack overflow storage for a launch of max_threads (0 = persistent grid)
 size_t pg_stack_overflow_words(uint64_t max_threads);
 // threads pg_launch_trace_rays launches for n rays (size its overflow ring with this)

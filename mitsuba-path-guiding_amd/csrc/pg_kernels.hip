@@ -246,7 +246,7 @@ __device__ __forceinline__ void shadowRows(const SceneDev &sc, const PathDev &p,
                 const float4 o = ldS(pathRayO(p, slot)), d = ldS(&p.sh_d[slot]);
                 if (!occluded(sc, xyz(o), xyz(d), shadowTmin(o), d.w, stk, tri)) shadowAdd(p, slot);
             }
-            if (blockerRowCounted(base / TRACE_BLOCK)) {  // pg_layout.h PG_BLOCKER_SAMPLE
+            if (sc.blk_counts && blockerRowCounted(base / TRACE_BLOCK)) {  // pg_layout.h PG_BLOCKER_SAMPLE
                 waveKeyedAdd<uint32_t>(sc.blk_counts, tri, 1u, tri != 0xFFFFFFFFu);
                 const unsigned long long rays = __ballot(i < n);
                 if ((threadIdx.x & 63) == 0 && rays) atomicAdd(sc.blk_total, (uint32_t)__popcll(rays));
@@ -281,30 +281,114 @@ __device__ __forceinline__ bool probeHit(const SceneDev &sc, float4 o, float4 d,
 // the probes of queue shard bid % PG_QSHARDS that block bid of nblk takes (a grid-stride loop as shadowRows'): no hit
 // record, no class queue; a wave adds its hits to the culled row and its misses to the escaped row of the counter
 // block the same launch's closest hits use, so the host's accounting sees them as it did when they were traced
+// Probe occluders (pg_layout.h): a probe the listed triangles resolve (pg_ray_hits_occluders: the walk is certain to
+// return a hit) is a hit without the walk, also counted in the queue's `dropped` row (pg_get_probes_resolved).  A walk
+// costs its wave what its slowest lane costs, so resolving most lanes of a wave saves nothing by itself: the probes a
+// row leaves unresolved are gathered in the wave's `pend` (PG_PROBE_PEND entries of LDS, the slot with bit 31 set on a
+// counted row) and walked 64 at a time by full waves, the rest after the last row.  An empty list costs the one
+// uniform branch: every row walks at once, as it did.
+// COUNT (the recording passes' instantiation, as shadowRows'): on the sampled rows every probe adds one to
+// sc.prb_counts[the triangle that answered it] -- the one its walk accepted, or the listed one that resolved it, so a
+// listed triangle keeps its share -- and the row's probes, hit or miss, to sc.prb_total.
+#define PG_PROBE_PEND 128u
+template <bool COUNT>
 __device__ __forceinline__ void probeRows(const SceneDev &sc, const PathDev &p, const Queue &q, const ClassQueues &cqs,
-                                          uint32_t bid, uint32_t nblk, const TStack &stk) {
+                                          uint32_t bid, uint32_t nblk, const TStack &stk, uint32_t *pend) {
     const uint32_t s = bid & (PG_QSHARDS - 1);
     const uint32_t n = q.counts[s];
     const uint32_t *items = q.items + (size_t)s * q.stride;
-    uint32_t hits = 0, misses = 0;
-    for (uint32_t i = (bid / PG_QSHARDS) * TRACE_BLOCK + threadIdx.x; i < n; i += nblk / PG_QSHARDS * TRACE_BLOCK) {
-        const uint32_t slot = items[i];
-        if (probeHit(sc, ldS(pathRayO(p, slot)), ldS(pathRayD(p, slot)), stk)) ++hits;
-        else ++misses;
+    const uint32_t lane = threadIdx.x & 63u;
+    const bool learn = COUNT && sc.prb_counts != nullptr;
+    uint32_t hits = 0, misses = 0, resolved = 0;
+    uint32_t held = 0;  // entries in pend (wave-uniform)
+    const uint32_t step = nblk / PG_QSHARDS * TRACE_BLOCK;
+    uint32_t base = (bid / PG_QSHARDS) * TRACE_BLOCK;
+    // block-uniform loop bounds: whole waves reach the ballots and the keyed adds together.  One iteration takes a row
+    // (while any is left), then walks at most once -- the row itself under an empty list, else 64 gathered probes, or
+    // what is left of them after the last row -- so the walk is compiled once.
+    while (base < n || held) {
+        float4 o = make_float4(0, 0, 0, 0), d = o;
+        bool active = false, counted = false, go = false;
+        if (base < n) {
+            const uint32_t i = base + threadIdx.x;
+            const bool rowCounted = learn && blockerRowCounted(base / TRACE_BLOCK);  // pg_layout.h PG_BLOCKER_SAMPLE
+            base += step;
+            uint32_t slot = 0;
+            if (i < n) {
+                slot = items[i];
+                o = ldS(pathRayO(p, slot));
+                d = ldS(pathRayD(p, slot));
+            }
+            if (rowCounted) {
+                const unsigned long long rays = __ballot(i < n);
+                if (lane == 0 && rays) atomicAdd(sc.prb_total, (uint32_t)__popcll(rays));
+            }
+            if (!sc.num_occluders) {
+                active = i < n;
+                counted = rowCounted;
+                go = true;
+            } else {
+                uint32_t listed = 0;
+                if (i < n) {
+                    const float po[3] = {o.x, o.y, o.z}, pd[3] = {d.x, d.y, d.z};
+                    listed = pg_ray_hits_occluders(sc.prb, sc.num_occluders, sc.absmax, po, pd, fabsf(o.w));
+                }
+                if (listed) {
+                    ++resolved;
+                    ++hits;
+                }
+                if (rowCounted) waveKeyedAdd<uint32_t>(sc.prb_counts, listed - 1u, 1u, listed != 0);
+                const bool open = i < n && !listed;
+                const unsigned long long m = __ballot(open);
+                // held < 64 here, so held + popc(m) <= 127 < PG_PROBE_PEND
+                if (open) pend[held + __popcll(m & ((1ull << lane) - 1ull))] = slot | (rowCounted ? 0x80000000u : 0u);
+                held += (uint32_t)__popcll(m);
+                // pend is the wave's own and a wave's LDS accesses complete in program order on gfx950 (lockstep lanes,
+                // one in-order LDS queue per wave), so a wavefront-scope fence is all that keeps the compiler from
+                // moving the reads below over these writes; no barrier, no other wave ever touches this part
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            }
+        }
+        if (sc.num_occluders && (held >= 64u || (base >= n && held))) {  // the top min(held, 64) entries of pend
+            const uint32_t m = held < 64u ? held : 64u;
+            held -= m;
+            active = lane < m;
+            if (active) {
+                const uint32_t e = pend[held + lane];
+                counted = (e >> 31) != 0;
+                o = ldS(pathRayO(p, e & 0x7FFFFFFFu));
+                d = ldS(pathRayD(p, e & 0x7FFFFFFFu));
+            }
+            go = true;
+        }
+        if (go) {
+            uint32_t tri = 0xFFFFFFFFu;
+            if (active) {
+                float tmax = __builtin_huge_valf(), u = 0, v = 0;
+                if (traverse<true>(sc.nodes, sc.tris, xyz(o), xyz(d), fabsf(o.w), tmax, tri, u, v, stk)) ++hits;
+                else ++misses;
+            }
+            if (learn) waveKeyedAdd<uint32_t>(sc.prb_counts, tri, 1u, counted && tri != 0xFFFFFFFFu);
+        }
     }
     for (int off = 32; off > 0; off >>= 1) {
         hits += __shfl_xor(hits, off);
         misses += __shfl_xor(misses, off);
+        resolved += __shfl_xor(resolved, off);
     }
-    if ((threadIdx.x & 63) == 0) {
+    if (lane == 0) {
         if (hits) atomicAdd(cqs.q[PG_CLASS_CULLED].counts + s, hits);
         if (misses) atomicAdd(cqs.q[PG_CLASS_ESCAPED].counts + s, misses);
+        if (resolved) atomicAdd(q.dropped + s, resolved);
     }
 }
 // the probes in a launch of their own (the unfused launches, PG_NO_RAYS_FUSION)
+template <bool COUNT>
 __global__ __launch_bounds__(TRACE_BLOCK) void k_probe(SceneDev sc, PathDev p, Queue q, ClassQueues cqs) {
     __shared__ uint32_t stack[LDS_STACK * TRACE_BLOCK];
-    probeRows(sc, p, q, cqs, blockIdx.x, gridDim.x, threadStack(stack, p.stack_ovf));
+    __shared__ uint32_t pend[PG_PROBE_PEND * (TRACE_BLOCK / 64)];
+    probeRows<COUNT>(sc, p, q, cqs, blockIdx.x, gridDim.x, threadStack(stack, p.stack_ovf),
+                     pend + PG_PROBE_PEND * (threadIdx.x / 64));
 }
 
 // a bounce's shadow rays and the next closest hits in one launch: blocks [0, shadow_blocks) run
@@ -323,9 +407,11 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PG_
                                                       Queue shq, uint32_t shadow_blocks, Queue pq, uint32_t probe_blocks) {
     // >= LDS_STACK words per thread
     __shared__ uint32_t stack[2 * WIDE_LDS_STACK * TRACE_BLOCK];
+    __shared__ uint32_t pend[PG_PROBE_PEND * (TRACE_BLOCK / 64)];  // probeRows' unresolved probes, per wave
     // the probe blocks come last
     if (blockIdx.x >= gridDim.x - probe_blocks) {
-        probeRows(sc, p, pq, cqs, blockIdx.x - (gridDim.x - probe_blocks), probe_blocks, threadStack(stack, p.stack_ovf));
+        probeRows<COUNT>(sc, p, pq, cqs, blockIdx.x - (gridDim.x - probe_blocks), probe_blocks,
+                         threadStack(stack, p.stack_ovf), pend + PG_PROBE_PEND * (threadIdx.x / 64));
         return;
     }
     const uint32_t trace_blocks = gridDim.x - probe_blocks - shadow_blocks;
@@ -1510,6 +1596,20 @@ __global__ __launch_bounds__(256) void k_blocker_test(SceneDev sc, const float *
     out[i] = pg_ray_hits_blockers(sc.blk, sc.num_blockers, sc.absmax, o, d, r[3], r[7]) ? 1u : 0u;
 }
 
+// pg_occluder_test: the tracer's occluder test and the probe walk on given rays (rows as k_trace_rays'; tmin in [3]):
+// out[2 i] = the test's answer, out[2 i + 1] = probeHit's
+__global__ __launch_bounds__(TRACE_BLOCK) void k_occluder_test(SceneDev sc, const float *__restrict__ rays, uint32_t n,
+                                                               uint32_t *__restrict__ out, uint32_t *ovf) {
+    __shared__ uint32_t stack[LDS_STACK * TRACE_BLOCK];
+    const TStack stk = threadStack(stack, ovf);
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *r = rays + 8 * (size_t)i;
+    const float o[3] = {r[0], r[1], r[2]}, d[3] = {r[4], r[5], r[6]};
+    out[2 * (size_t)i] = pg_ray_hits_occluders(sc.prb, sc.num_occluders, sc.absmax, o, d, fabsf(r[3])) ? 1u : 0u;
+    out[2 * (size_t)i + 1] = probeHit(sc, make_float4(r[0], r[1], r[2], r[3]), make_float4(r[4], r[5], r[6], 0.0f), stk) ? 1u : 0u;
+}
+
 __global__ __launch_bounds__(256) void k_bsdf_query(const GMat *mat, const float *wi, const float *u, const float *wog,
                                                     uint32_t n, float *out) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1688,12 +1788,15 @@ void pg_launch_shade_all(hipStream_t s, const GParams &g, const SceneDev &sc, co
 }
 // the recording passes count shadow blockers (sc.blk_counts is set only for them, never with an environment emitter)
 static inline bool blockersCounted(const GParams &g, const SceneDev &sc) { return g.record && sc.blk_counts && !sc.env; }
+// ... and the probe rows their occluders (sc.prb_counts, set as blk_counts is).  k_rays<false, true> serves either, so
+// its rows check their own pointer.
+static inline bool probesCounted(const SceneDev &sc) { return sc.prb_counts && !sc.env; }
 void pg_launch_rays(hipStream_t s, const GParams &g, const SceneDev &sc, const PathDev &p, Queue q, uint32_t max_shard,
                     const Queue *class_queues, Queue shq, uint32_t max_shadow_shard, Queue pq) {
     ClassQueues cq;
     for (int c = 0; c < PG_CLASS_ROWS; ++c) cq.q[c] = class_queues[c];
     const uint32_t sb = max_shadow_shard ? shardGrid(max_shadow_shard, TRACE_BLOCK, TRACE_MAX_BLOCKS / PG_QSHARDS).x : 0;
-    const bool count = blockersCounted(g, sc);
+    const bool count = blockersCounted(g, sc), pcount = probesCounted(sc);
     // the probe queue's shards are bounded as the shadow queue's (both hold vertices of the bounce just shaded)
     const uint32_t pb = (g.doom_probe && !sc.env) ? sb : 0;
     const uint32_t tb =
@@ -1702,12 +1805,13 @@ void pg_launch_rays(hipStream_t s, const GParams &g, const SceneDev &sc, const P
     if (tb == 0) {  // no trace rows: k_rays needs at least one trace block per shard to stay sharded
         if (count) hipLaunchKernelGGL(k_shadow<true>, dim3(sb), dim3(TRACE_BLOCK), 0, s, sc, p, shq);
         else hipLaunchKernelGGL(k_shadow<false>, dim3(sb), dim3(TRACE_BLOCK), 0, s, sc, p, shq);
-        if (pb) hipLaunchKernelGGL(k_probe, dim3(pb), dim3(TRACE_BLOCK), 0, s, sc, p, pq, cq);
+        if (pb && pcount) hipLaunchKernelGGL(k_probe<true>, dim3(pb), dim3(TRACE_BLOCK), 0, s, sc, p, pq, cq);
+        else if (pb) hipLaunchKernelGGL(k_probe<false>, dim3(pb), dim3(TRACE_BLOCK), 0, s, sc, p, pq, cq);
         return;
     }
     // sb + tb + pb <= 3 TRACE_MAX_BLOCKS: the overflow ring's size (pg_host.cpp ensurePaths)
     if (sc.env) hipLaunchKernelGGL(k_rays<true>, dim3(sb + tb + pb), dim3(TRACE_BLOCK), 0, s, g, sc, p, q, cq, shq, sb, pq, pb);
-    else if (count) hipLaunchKernelGGL((k_rays<false, true>), dim3(sb + tb + pb), dim3(TRACE_BLOCK), 0, s, g, sc, p, q, cq, shq, sb, pq, pb);
+    else if (count || pcount) hipLaunchKernelGGL((k_rays<false, true>), dim3(sb + tb + pb), dim3(TRACE_BLOCK), 0, s, g, sc, p, q, cq, shq, sb, pq, pb);
     else hipLaunchKernelGGL(k_rays<false>, dim3(sb + tb + pb), dim3(TRACE_BLOCK), 0, s, g, sc, p, q, cq, shq, sb, pq, pb);
 }
 void pg_launch_probe(hipStream_t s, const SceneDev &sc, const PathDev &p, Queue pq, uint32_t max_shard,
@@ -1715,8 +1819,9 @@ void pg_launch_probe(hipStream_t s, const SceneDev &sc, const PathDev &p, Queue 
     if (!max_shard) return;
     ClassQueues cq;
     for (int c = 0; c < PG_CLASS_ROWS; ++c) cq.q[c] = class_queues[c];
-    hipLaunchKernelGGL(k_probe, shardGrid(max_shard, TRACE_BLOCK, TRACE_MAX_BLOCKS / PG_QSHARDS), dim3(TRACE_BLOCK), 0, s,
-                       sc, p, pq, cq);
+    const dim3 grid = shardGrid(max_shard, TRACE_BLOCK, TRACE_MAX_BLOCKS / PG_QSHARDS);
+    if (probesCounted(sc)) hipLaunchKernelGGL(k_probe<true>, grid, dim3(TRACE_BLOCK), 0, s, sc, p, pq, cq);
+    else hipLaunchKernelGGL(k_probe<false>, grid, dim3(TRACE_BLOCK), 0, s, sc, p, pq, cq);
 }
 void pg_launch_shadow(hipStream_t s, const GParams &g, const SceneDev &sc, const PathDev &p, Queue q, uint32_t max_shard) {
     if (!max_shard) return;
@@ -1904,6 +2009,11 @@ void pg_launch_hit_uvs(hipStream_t s, const SceneDev &sc, const float *rays, uin
 void pg_launch_blocker_test(hipStream_t s, const SceneDev &sc, const float *rays, uint32_t n, uint32_t *out) {
     if (!n) return;
     hipLaunchKernelGGL(k_blocker_test, dim3(blocks(n, 256)), dim3(256), 0, s, sc, rays, n, out);
+}
+// n rays in blocks(n, TRACE_BLOCK) blocks, as k_trace_rays: ovf holds pg_stack_overflow_words(pg_trace_rays_threads(n))
+void pg_launch_occluder_test(hipStream_t s, const SceneDev &sc, const float *rays, uint32_t n, uint32_t *out, uint32_t *ovf) {
+    if (!n) return;
+    hipLaunchKernelGGL(k_occluder_test, dim3(blocks(n, TRACE_BLOCK)), dim3(TRACE_BLOCK), 0, s, sc, rays, n, out, ovf);
 }
 void pg_launch_bsdf_query(hipStream_t s, const GMat *mat, const float *wi, const float *u, const float *wog, uint32_t n,
                           float *out) {

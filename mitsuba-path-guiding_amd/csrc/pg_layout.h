@@ -413,16 +413,14 @@ inline uint32_t pg_emitter_boxes(const float *positions, const uint32_t *indices
 // blk: the listed records, 12 floats each: TriAccel rows 0-2 with [10] = bits(BVH-order id) and [11] = the smaller
 // width of the triangle's box on the two axes other than k.  absmax: the scene's largest |coordinate|.
 // Returns 1 + the id ([10]) of the first listed triangle that certainly blocks o + t d, t in [tmin, tmax]; 0: none.
-PG_HD inline uint32_t pg_ray_hits_blockers(const float (*blk)[12], uint32_t n, float absmax, const float o[3],
-                                           const float d[3], float tmin, float tmax) {
+// The listed-record loop of both certain-hit tests (this one and pg_ray_hits_occluders below): the first record whose
+// TriAccel test, in triHitRow0's arithmetic, puts the hit at t in [tlo, thi] with every barycentric weight >=
+// PG_BLOCKER_MARGIN, on a triangle wide enough for E and not grazed by d.  1 + its id ([10]); 0: none.
+PG_HD inline uint32_t pg_ray_hits_records(const float (*blk)[12], uint32_t n, float E, float dmax, const float o[3],
+                                          const float d[3], float tlo, float thi) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
-    const float E = absmax + fmaxf(fmaxf(fabsf(o[0]), fabsf(o[1])), fabsf(o[2]));
-    const float dmax = fmaxf(fmaxf(fabsf(d[0]), fabsf(d[1])), fabsf(d[2]));
-    const float dmin = fminf(fminf(fabsf(d[0]), fabsf(d[1])), fabsf(d[2]));
-    if (!(dmin > 1e-30f && tmax * dmax * 32.0f >= E)) return 0;
-    const float shrink = PG_BLOCKER_MARGIN * tmax;
     for (uint32_t b = 0; b < n; ++b) {
         const float *r = blk[b];
         uint32_t k;
@@ -436,7 +434,7 @@ PG_HD inline uint32_t pg_ray_hits_blockers(const float (*blk)[12], uint32_t n, f
         const float den = du * r[0] + dv * r[1] + dk;
         if (!(fabsf(dk) * 16.0f >= dmax && fabsf(den) * 16.0f >= dmax)) continue;
         const float tt = (r[2] - ou * r[0] - ov * r[1] - ok) / den;
-        if (!(tt >= tmin + shrink && tt <= tmax - shrink)) continue;
+        if (!(tt >= tlo && tt <= thi)) continue;
         const float hu = ou + tt * du - r[4], hv = ov + tt * dv - r[5];
         const float u = hv * r[6] + hu * r[7];
         const float v = hu * r[8] + hv * r[9];
@@ -447,6 +445,18 @@ PG_HD inline uint32_t pg_ray_hits_blockers(const float (*blk)[12], uint32_t n, f
         }
     }
     return 0;
+}
+PG_HD inline uint32_t pg_ray_hits_blockers(const float (*blk)[12], uint32_t n, float absmax, const float o[3],
+                                           const float d[3], float tmin, float tmax) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const float E = absmax + fmaxf(fmaxf(fabsf(o[0]), fabsf(o[1])), fabsf(o[2]));
+    const float dmax = fmaxf(fmaxf(fabsf(d[0]), fabsf(d[1])), fabsf(d[2]));
+    const float dmin = fminf(fminf(fabsf(d[0]), fabsf(d[1])), fabsf(d[2]));
+    if (!(dmin > 1e-30f && tmax * dmax * 32.0f >= E)) return 0;
+    const float shrink = PG_BLOCKER_MARGIN * tmax;
+    return pg_ray_hits_records(blk, n, E, dmax, o, d, tmin + shrink, tmax - shrink);
 }
 // Host: the listed record of BVH-order triangle `id`: its TriAccel rows (3 float4), p0 / p1 / p2 its vertices
 inline void pg_blocker_record(const float *rows, const float *p0, const float *p1, const float *p2, uint32_t id,
@@ -467,7 +477,8 @@ inline void pg_blocker_record(const float *rows, const float *p0, const float *p
 // number of shadow rays (occluded or not) the counts were taken from: below that share eight tests per NEE vertex
 // cannot pay for themselves.  Equal counts go to the lower id, so the list is reproducible.  The list is empty
 // unless its triangles together blocked at least half of the total.  Returns the number written to ids.
-inline uint32_t pg_select_blockers(const uint32_t *counts, uint32_t n, uint64_t total, uint32_t *ids) {
+// pg_select_listed: the rule with the list's capacity `cap` as a parameter (the probe occluders' list is longer)
+inline uint32_t pg_select_listed(const uint32_t *counts, uint32_t n, uint64_t total, uint32_t cap, uint32_t *ids) {
     uint32_t m = 0;
     if (!total) return 0;
     for (uint32_t t = 0; t < n; ++t) {
@@ -476,15 +487,76 @@ inline uint32_t pg_select_blockers(const uint32_t *counts, uint32_t n, uint64_t 
         // insertion into the descending list; strict > keeps the lower id first among equals
         uint32_t at = m;
         while (at > 0 && c > counts[ids[at - 1]]) --at;
-        if (at >= PG_MAX_BLOCKERS) continue;
-        const uint32_t last = m < PG_MAX_BLOCKERS ? m : PG_MAX_BLOCKERS - 1;
+        if (at >= cap) continue;
+        const uint32_t last = m < cap ? m : cap - 1;
         for (uint32_t j = last; j > at; --j) ids[j] = ids[j - 1];
         ids[at] = t;
-        if (m < PG_MAX_BLOCKERS) ++m;
+        if (m < cap) ++m;
     }
     uint64_t listed = 0;
     for (uint32_t j = 0; j < m; ++j) listed += counts[ids[j]];
     return 2 * listed >= total ? m : 0;
+}
+inline uint32_t pg_select_blockers(const uint32_t *counts, uint32_t n, uint64_t total, uint32_t *ids) {
+    return pg_select_listed(counts, n, total, PG_MAX_BLOCKERS, ids);
+}
+
+// Probe occluders (SceneDev::prb): a doom probe (above) only asks whether its ray hits anything, and in a closed
+// room nearly every probe does -- after a nearest-first descent almost as long as a closest-hit walk's.  The probe
+// rows of the recording passes count, per triangle, the probes whose walk accepted it (every PG_BLOCKER_SAMPLE-th row,
+// counters of their own beside the shadow blockers', the same selection rule: pg_select_listed with up to
+// PG_PROBE_LIST_MAX triangles).  The tracing kernels then test a probe against the listed records first
+// (pg_kernels.hip probeRows): a certain hit is counted as the hit the walk would have returned, without the walk.
+// Any listed triangle hit anywhere along the ray will do, whatever lies in front of it: the walk cannot end without a
+// hit while a triangle it is certain to accept is still ahead.  The list only decides which probes skip the walk,
+// never a counter: `culled`, `escaped` and `probes` keep their values, a resolved probe is also counted in a row of
+// its own (pg_get_probes_resolved).
+//
+// "Certain" (pg_ray_hits_occluders): "hit" only where probeHit -- the any-hit form of the 4-wide closest-hit walk
+// (pg_trace.h traverse4), tmin = |ray_o.w|, tmax = +inf -- says it too.  That walk returns only at its first accepted
+// triangle or with an empty stack (the builder holds its trees under PG_QSTACK_DEPTH), so it either accepts some
+// triangle first or reaches every leaf whose ancestor slots all pass; in the listed triangle's leaf its test is
+// pg_ray_hits_records' arithmetic bit for bit (same record, o, d, tmin; t <= inf, and t < inf always accepts), whose
+// margins are stricter than the leaf's u, v >= 0, u + v <= 1, t >= tmin.  So it is enough that every ancestor slot
+// passes cmin <= cmax (1 + 2^-21), cmin = max(tn_x, tn_y, tn_z, tmin), cmax = min(tf_x, tf_y, tf_z, inf).  The slot's
+// planes X = origin + q 2^e are rounded outward, so they enclose the triangle.  The walk computes t = fma(q, 2^e idir,
+// fma(origin, idir, -(o idir) -+ pad_o) -+ pad_n): 2^e idir is exact, and the roundings of idir, o idir, the padded
+// addend, both fmas and the last subtraction displace a plane by at most 6 * 2^-24 E < d_pos = 2^-21 E along its axis
+// (E as for the blockers: |origin|, |X - o| <= E to first order).  Its paddings (2^-21 |o_a|, 2^-22 |origin_a|) only
+// move the near plane earlier and the far plane later, and (1 + 2^-21) only loosens the comparison where cmax > 0.
+// The unpadded 8-wide walk of the blockers' derivation is therefore the stricter of the two, and the same margins
+// hold: barycentrics >= 2^-10 on a triangle at least E / 32 wide off its axis k (the hit point is >= 2^-16 E inside
+// the box on both wide axes, 2 d_pos between them, 17 d_pos against the flat axis), |d_k|, |den| >= max|d| / 16, no
+// |d_a| <= 1e-30.  What changes is the interval: there is no tmax, so the blockers' shrink 2^-10 tmax with tmax max|d|
+// >= E / 32 becomes its smallest admissible value, t >= tmin + 2^-15 E / max|d|: the flat axis' far plane is computed at
+// t - (d_pos / |d_k| + the error of t) >= t - 1.5 * 2^-17 E / max|d| >= tmin, so cmax >= tmin > 0 and tmin never cuts
+// the slot; t must be finite.
+// A probe that fails any margin, or hits no listed triangle, walks as before.
+#define PG_PROBE_LIST_MAX 16
+#define PG_PROBE_TMIN_MARGIN 3.0517578125e-5f  // 2^-15
+// prb: the listed records (pg_blocker_record's form).  Returns 1 + the id of the first listed triangle the probe
+// walk of o + t d, t >= tmin, is certain to end on or before; 0: none (the walk decides).
+PG_HD inline uint32_t pg_ray_hits_occluders(const float (*prb)[12], uint32_t n, float absmax, const float o[3],
+                                            const float d[3], float tmin) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const float E = absmax + fmaxf(fmaxf(fabsf(o[0]), fabsf(o[1])), fabsf(o[2]));
+    const float dmax = fmaxf(fmaxf(fabsf(d[0]), fabsf(d[1])), fabsf(d[2]));
+    const float dmin = fminf(fminf(fabsf(d[0]), fabsf(d[1])), fabsf(d[2]));
+    if (!(dmin > 1e-30f)) return 0;
+    const float tlo = tmin + PG_PROBE_TMIN_MARGIN * E / dmax;
+    // one record per call, the loop unrolled: every index into the by-value list is then a constant and the records
+    // are read from the kernel arguments (a run-time index had the kernels copy the list to 1.6 KB of scratch per lane)
+#if defined(__clang__)
+#pragma unroll
+#endif
+    for (uint32_t b = 0; b < PG_PROBE_LIST_MAX; ++b) {
+        if (b >= n) break;
+        const uint32_t hit = pg_ray_hits_records(prb + b, 1, E, dmax, o, d, tlo, 3.40282347e38f);
+        if (hit) return hit;
+    }
+    return 0;
 }
 
 // Kernel-side constants of one render context.

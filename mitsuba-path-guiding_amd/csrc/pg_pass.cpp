@@ -529,6 +529,7 @@ pg_status collectStats(Ctx *c, Lane &l) {
             // shadow rays the shader resolved: never queued, still shadow rays of the job
             c->stats.shadow_rays += l.h_stats[(size_t)kBounceWords * k + kDropCounts + sh];
             c->shadow_culled += l.h_stats[(size_t)kBounceWords * k + kDropCounts + sh];
+            c->probes_resolved += l.h_stats[(size_t)kBounceWords * k + kResolvedCounts + sh];
         }
     c->stats.segments += l.h_tail[0];  // the chunk's tail (k_tail)
     c->stats.escaped += l.h_tail[1];
@@ -656,6 +657,12 @@ pg_status renderPass(Ctx *c, uint32_t spp, uint32_t sample_offset, int32_t recor
     // walk; PG_NO_DOOM_PROBE=1 (or no path cull) traces them all as before (same results).  Never with an environment
     // emitter: an escaping doomed ray picks up its radiance.
     g.doom_probe = (g.path_cull && !c->has_env && !std::getenv("PG_NO_DOOM_PROBE")) ? 1 : 0;
+    // ... and count the triangles their probes end on (pg_layout.h "Probe occluders"), in the second half of blk_counts
+    const bool learnProbes = rec && g.doom_probe && !c->prb_stopped && probeListEnabled(c);
+    if (learnProbes) {
+        sc.prb_counts = c->blk_counts.as<uint32_t>() + c->num_tris + 1;
+        sc.prb_total = sc.prb_counts + c->num_tris;
+    }
     const bool bands = cameraBands() > 0;
     const bool fuseShade = !c->has_env && !std::getenv("PG_NO_SHADE_FUSION");
     // chunks: whole sample layers over the local pixels when they fit, else pixel ranges
@@ -795,7 +802,8 @@ pg_status renderPass(Ctx *c, uint32_t spp, uint32_t sample_offset, int32_t recor
         Queue next = lqueue(l, (l.b & 1) ? l.q1.as<uint32_t>() : l.q0.as<uint32_t>(), cb + kBounceWords);
         Queue shq = lqueue(l, l.qs.as<uint32_t>(), cb + kShadowCounts);
         shq.dropped = cb + kDropCounts;
-        const Queue pq = lqueue(l, l.qp.as<uint32_t>(), cb + kProbeCounts);
+        Queue pq = lqueue(l, l.qp.as<uint32_t>(), cb + kProbeCounts);
+        pq.dropped = cb + kResolvedCounts;
         const uint32_t nextBound = *std::max_element(shardLive, shardLive + PG_QSHARDS);
         const bool sortNext = raySortEnabled() && nextBound >= kRaySortMinShard;
         if (sortNext) next.keys = l.qkey.as<uint16_t>();
@@ -854,7 +862,7 @@ pg_status renderPass(Ctx *c, uint32_t spp, uint32_t sample_offset, int32_t recor
     }
     if (rec && (s = foldRecordCount(c))) return s;
     HIPC(c, hipStreamSynchronize(c->stream));
-    if (learn && (s = learnBlockers(c))) return s;
+    if ((learn || learnProbes) && (s = learnBlockers(c, learn, learnProbes))) return s;
     return PG_OK;
 }
 

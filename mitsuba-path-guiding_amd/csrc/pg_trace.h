@@ -308,9 +308,9 @@ __device__ __forceinline__ bool leafTest(const float4 *__restrict__ tris, int le
             float tt, bu, bv;
             if (k + j < cnt && triHitRow0(r[j], tris, tr, o, d, tmin, tmax, tt, bu, bv) && acceptHit(tris, tt, tmax, tr, hitTri)) {
                 found = true;
+                hitTri = tr;  // an any-hit walk's accepted triangle too (probeRows counts it)
                 if (ANY) return true;
                 tmax = tt;
-                hitTri = tr;
                 hu = bu;
                 hv = bv;
             }
