@@ -157,6 +157,12 @@ __host__ __device__ inline uint32_t pg_camera_shard_count(uint32_t n, uint32_t s
     int rem = (int)(n & 4095u) - 64 * (int)s;
     return 64u * (n >> 12) + (uint32_t)(rem < 0 ? 0 : rem > 64 ? 64 : rem);
 }
+// the interleaved camera map in closed form: entry i of shard s holds this slot, for i < pg_camera_shard_count(n, s).
+// pg_camera_shard / pg_camera_entry are the same map forwards.  k_camera stores it; the fused first launch
+// (k_camera_trace) computes it, so there the camera queue is neither stored nor loaded
+__host__ __device__ inline uint32_t pg_camera_slot(uint32_t s, uint32_t i) { return ((i >> 6) << 12) | (s << 6) | (i & 63u); }
+__host__ __device__ inline uint32_t pg_camera_shard(uint32_t slot) { return (slot >> 6) & 63u; }
+__host__ __device__ inline uint32_t pg_camera_entry(uint32_t slot) { return ((slot >> 12) << 6) | (slot & 63u); }
 // XCD-banded camera map (round 6, PG_CAMERA_BANDS): blocks b and b + 8 run on one XCD (MI355X_MICROARCH.md
 // §Workgroup dispatch) and every sharded launch gives block b shard b % 64, so shards s and s + 8 share an XCD's
 // L2 for the paths' whole lives.  The banded map deals the chunk's pixels in 8 contiguous bands (local pixel
@@ -201,6 +207,15 @@ void pg_launch_camera_rays(hipStream_t s, const GParams &g, const uint32_t *pixe
 // first_bounce: the chunk's camera rays (their hit records are kept in p.aov when it is set)
 void pg_launch_trace(hipStream_t s, const GParams &g, const SceneDev &sc, const PathDev &p, Queue q, uint32_t max_shard,
                      const Queue *class_queues, bool first_bounce);
+// a chunk's first launch with the camera rays generated in it: pg_launch_camera (interleaved map) + pg_launch_trace
+// (first_bounce) in one, without the camera queue, ray_o and the ray read-back between them.  Same grid, same slots per
+// lane, same results; the largest shard is pg_camera_bound(false, npix, nlayers)
+void pg_launch_camera_trace(hipStream_t s, const GParams &g, const SceneDev &sc, const PathDev &p,
+                            const uint32_t *local_pixels, uint32_t pix_begin, uint32_t npix, uint32_t nlayers,
+                            uint32_t sample_base, const Queue *class_queues);
+// the interleaved camera queue (items and counts) of a chunk, as pg_launch_camera fills it: for pg_launch_tail on a
+// chunk whose first launch was pg_launch_camera_trace
+void pg_launch_camera_queue(hipStream_t s, uint32_t npix, uint32_t nlayers, Queue q);
 // probe: the doomed rays that miss every emitter box (pg_layout.h "Doom probe"), answered by pg_launch_rays / _probe
 void pg_launch_shade_class(hipStream_t s, int cls, const GParams &g, const SceneDev &sc, const SDDev &sd,
                            const PathDev &p, Queue in, uint32_t max_shard, Queue out, Queue shadow, Queue probe);

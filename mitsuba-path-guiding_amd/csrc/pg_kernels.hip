@@ -48,9 +48,16 @@ __global__ __launch_bounds__(256) void k_camera(GParams g, PathDev p, const uint
         const uint32_t b0 = pg_band_start(r, npix), m = pg_band_start(r + 1, npix) - b0;
         const uint32_t k = layer * m + (lp - b0);
         q.items[(r + 8u * ((k >> 6) & 7u)) * q.stride + (((k >> 9) << 6) | (k & 63u))] = slot;
-    } else {
-        q.items[((slot >> 6) & 63u) * q.stride + (((slot >> 12) << 6) | (slot & 63u))] = slot;
+    } else {  // pg_kernels.h pg_camera_slot: the fused first launch (cameraRows) computes this entry instead
+        q.items[pg_camera_shard(slot) * q.stride + pg_camera_entry(slot)] = slot;
     }
+}
+// the interleaved camera queue alone: what k_camera stores in q, for the one reader the fused first launch leaves it
+// (k_tail, when it takes a chunk over straight after the camera rays' hits)
+__global__ __launch_bounds__(256) void k_camera_queue(uint32_t n, Queue q) {
+    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot < PG_QSHARDS) q.counts[slot] = pg_camera_shard_count(n, slot);
+    if (slot < n) q.items[pg_camera_shard(slot) * q.stride + pg_camera_entry(slot)] = slot;
 }
 
 // BSDF::getAlbedo of the config BSDFs (diffuse.cpp:112, conductor.cpp:225, roughconductor.cpp:264,
@@ -201,6 +208,62 @@ __global__ __launch_bounds__(TRACE_BLOCK) void k_trace(GParams g, SceneDev sc, P
                                                        float4 *first) {
     __shared__ uint32_t stack[LDS_STACK * TRACE_BLOCK];
     traceRows<ENV, CAM>(g, sc, p, q, cqs, first, blockIdx.x, gridDim.x, threadStack(stack, p.stack_ovf));
+}
+
+// A chunk's camera rays, generated where they are traced (the chunk's first launch; k_camera + k_trace<ENV, true> in one,
+// DESIGN.md section 5 "Camera fusion").  The rows are those of the interleaved camera queue, which is never stored: entry
+// i of shard s is slot pg_camera_slot(s, i) and the shard holds pg_camera_shard_count entries, so blocks, waves and
+// lanes take the slots they took when the queue was read back.  Of k_camera's rows ray_d, pinfo and rad = 0 are stored
+// (pg_layout.h "Path state"); ray_o, the near clip and the queue entry have no reader after this launch.
+struct CameraChunk {
+    const uint32_t *local_pixels;
+    uint32_t pix_begin, npix, nlayers, sample_base;
+};
+template <bool ENV, bool LENS>
+__device__ __forceinline__ void cameraRows(const GParams &g, const SceneDev &sc, const PathDev &p, const CameraChunk &cam,
+                                           const ClassQueues &cqs, float4 *first, uint32_t bid, uint32_t nblk,
+                                           const TStack &stk) {
+    const uint32_t s = bid & (PG_QSHARDS - 1);
+    const uint32_t n = pg_camera_shard_count(cam.npix * cam.nlayers, s);
+    // block-uniform loop bound, as traceRows'
+    for (uint32_t base = (bid / PG_QSHARDS) * TRACE_BLOCK; base < n; base += nblk / PG_QSHARDS * TRACE_BLOCK) {
+        const uint32_t i = base + threadIdx.x;
+        int cls = -1;
+        uint32_t slot = 0;
+        if (i < n) {
+            slot = pg_camera_slot(s, i);
+            f3 o, wd;
+            float tmin, tmax;
+            {  // k_camera's rows
+                const uint32_t layer = slot / cam.npix, lp = slot - layer * cam.npix;
+                const uint32_t pix = cam.local_pixels[cam.pix_begin + lp];
+                const uint32_t sample = cam.sample_base + layer;
+                cameraRay<LENS>(g, pix, rngKey(pix, g.seed), sample, o, wd, tmin, tmax);
+                stS(pathRayD(p, slot), f4(wd, tmax));
+                stS(&p.rad[slot], make_float4(0.f, 0.f, 0.f, 0.f));
+                stS(pathInfo(p, slot), make_uint4(pix, sample, kCameraWord, 0u));
+            }
+            const float far = tmax;
+            uint32_t tri = 0xFFFFFFFFu;
+            float u = 0, v = 0;
+            const bool h = traverse<false>(sc.nodes, sc.tris, o, wd, tmin, tmax, tri, u, v, stk);
+            float4 hr = make_float4(h ? tmax : 0.0f, __uint_as_float(h ? tri : 0xFFFFFFFFu), u, v);
+            if (first) first[slot] = hr;
+            if (ENV && !h) {
+                const f3 e = envEscapeRadiance(g, sc, p, slot, wd, kCameraWord, far);
+                hr = make_float4(e.x, hr.y, e.y, e.z);
+            }
+            cls = hitClass(sc, h, tri, false, hr);
+            stS(&p.hit[slot], hr);
+        }
+        classAppend(cls, slot, cqs, s);
+    }
+}
+template <bool ENV, bool LENS>
+__global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(LENS ? 4 : ENV ? 5 : 6))) void k_camera_trace(GParams g, SceneDev sc, PathDev p, CameraChunk cam,
+                                                              ClassQueues cqs, float4 *first) {
+    __shared__ uint32_t stack[LDS_STACK * TRACE_BLOCK];
+    cameraRows<ENV, LENS>(g, sc, p, cam, cqs, first, blockIdx.x, gridDim.x, threadStack(stack, p.stack_ovf));
 }
 
 // shadow-ray mint at the shading point o (the extension ray's origin): Epsilon * max |o_i|
@@ -1729,6 +1792,29 @@ void pg_launch_trace(hipStream_t s, const GParams &g, const SceneDev &sc, const 
         if (sc.env) hipLaunchKernelGGL((k_trace<true, false>), grid, dim3(TRACE_BLOCK), 0, s, g, sc, p, q, cq, first);
         else hipLaunchKernelGGL((k_trace<false, false>), grid, dim3(TRACE_BLOCK), 0, s, g, sc, p, q, cq, first);
     }
+}
+void pg_launch_camera_trace(hipStream_t s, const GParams &g, const SceneDev &sc, const PathDev &p,
+                            const uint32_t *local_pixels, uint32_t pix_begin, uint32_t npix, uint32_t nlayers,
+                            uint32_t sample_base, const Queue *class_queues) {
+    const uint32_t max_shard = pg_camera_bound(false, npix, nlayers);
+    if (!max_shard) return;
+    ClassQueues cq;
+    for (int c = 0; c < PG_CLASS_ROWS; ++c) cq.q[c] = class_queues[c];
+    const dim3 grid = shardGrid(max_shard, TRACE_BLOCK, TRACE_MAX_BLOCKS / PG_QSHARDS), block(TRACE_BLOCK);
+    const CameraChunk cam{local_pixels, pix_begin, npix, nlayers, sample_base};
+    const bool lens = g.lens_radius > 0;
+    if (sc.env) {
+        if (lens) hipLaunchKernelGGL((k_camera_trace<true, true>), grid, block, 0, s, g, sc, p, cam, cq, p.aov);
+        else hipLaunchKernelGGL((k_camera_trace<true, false>), grid, block, 0, s, g, sc, p, cam, cq, p.aov);
+    } else {
+        if (lens) hipLaunchKernelGGL((k_camera_trace<false, true>), grid, block, 0, s, g, sc, p, cam, cq, p.aov);
+        else hipLaunchKernelGGL((k_camera_trace<false, false>), grid, block, 0, s, g, sc, p, cam, cq, p.aov);
+    }
+}
+void pg_launch_camera_queue(hipStream_t s, uint32_t npix, uint32_t nlayers, Queue q) {
+    const uint64_t n = (uint64_t)npix * nlayers;
+    if (!n) return;
+    hipLaunchKernelGGL(k_camera_queue, dim3(blocks(n, 256)), dim3(256), 0, s, (uint32_t)n, q);
 }
 template <bool ENV, bool DELTA>
 static void launchShade(hipStream_t s, int cls, dim3 grid, const GParams &g, const SceneDev &sc, const SDDev &sd,

@@ -230,9 +230,16 @@ inline void pg_qnode_box(const float *node, int s, float lo[3], float hi[3]) {
 // section 5 "Paired state"); hit, rad, sh_d and sh_c are arrays of their own, one row per slot:
 //   ray[2 slot] = ray_o, ray[2 slot + 1] = ray_d     (pathRayO, pathRayD)
 //   vst[2 slot] = pinfo, vst[2 slot + 1] = thr       (pathInfo, pathThr)
-//   camera ray (k_camera):  ray_o = (camera position, near clip along the ray)   ray_d = (direction, far clip)
+//   camera ray (k_camera_trace, the chunk's first launch: generated and traced there, DESIGN.md section 5 "Camera
+//                           fusion"):  ray_d = (direction, far clip); the far clip has no reader (the walk that takes
+//                           it is in the same launch), a depth-1 vertex reads the direction only
 //                           pinfo = (pixel, sample, 1 | PF_EMITTED_QUERY << 16, 0)   rad = 0   thr: implied (1, eta 1),
-//                           its half of the record keeps what the slot's previous path left there
+//                           its half of the record keeps what the slot's previous path left there, and so does ray_o:
+//                           the origin and the near clip are not stored (shadeOne recomputes the hit point from the
+//                           barycentrics and stores ray_o before anything reads it), nor is the camera queue
+//                           (pg_kernels.h pg_camera_slot).  PG_NO_CAMERA_FUSION=1 and PG_CAMERA_BANDS run k_camera +
+//                           k_trace<., true>: k_camera stores ray_o = (camera position, near clip along the ray) and
+//                           the queue as well, and k_trace reads them back
 //   bounce ray (shadeOne):  ray_o = (p, +-tmin)   ray_d = (wo, woPdf)   thr = (T, eta)
 //                           pinfo.zw = (depth | flags << 16, training-vertex count), an 8-B store: with thr one
 //                           contiguous 24-B span of the vst record

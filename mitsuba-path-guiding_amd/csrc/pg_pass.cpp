@@ -664,6 +664,10 @@ pg_status renderPass(Ctx *c, uint32_t spp, uint32_t sample_offset, int32_t recor
         sc.prb_total = sc.prb_counts + c->num_tris;
     }
     const bool bands = cameraBands() > 0;
+    // a chunk's first launch generates the camera rays it traces (k_camera_trace, DESIGN.md section 5 "Camera fusion");
+    // PG_NO_CAMERA_FUSION=1 launches the pair k_camera + k_trace as before (same results), and so does the banded
+    // camera map, which has no closed-form inverse
+    const bool fuseCamera = !bands && !std::getenv("PG_NO_CAMERA_FUSION");
     const bool fuseShade = !c->has_env && !std::getenv("PG_NO_SHADE_FUSION");
     // chunks: whole sample layers over the local pixels when they fit, else pixel ranges
     const std::vector<VChunk> chunks = planChunks(npix, spp, want, sample_offset);
@@ -699,6 +703,9 @@ pg_status renderPass(Ctx *c, uint32_t spp, uint32_t sample_offset, int32_t recor
         if (evt) HIPC(c, hipEventRecord(et.a, l.stream));
         const Queue tq = traceQueue(l, l.b);
         if (shq) pg_launch_rays(l.stream, g, sc, pathView(&l), tq, l.bound, cls, *shq, l.bound, *pq);
+        else if (l.b == 0 && fuseCamera)  // the chunk's trace launch, the camera rays generated in it
+            pg_launch_camera_trace(l.stream, g, sc, pathView(&l), c->d_band_pixels.as<uint32_t>(), l.pb, l.np, l.nl,
+                                   l.sample_base, cls);
         else pg_launch_trace(l.stream, g, sc, pathView(&l), tq, l.bound, cls, l.b == 0);
         if (evt) HIPC(c, hipEventRecord(et.b, l.stream));
         HIPC(c, hipMemcpyAsync(l.h_counts + (size_t)kBounceWords * l.b + kClassCounts, cb + kClassCounts,
@@ -722,8 +729,9 @@ pg_status renderPass(Ctx *c, uint32_t spp, uint32_t sample_offset, int32_t recor
         HIPC(c, hipStreamWaitEvent(l.stream, c->pass_start, 0));
         HIPC(c, hipMemsetAsync(l.counters.p, 0, (size_t)kBounceWords * (maxBounces + 1) * 4, l.stream));
         HIPC(c, hipMemsetAsync(l.tail_stats.p, 0, kTailStats * 8, l.stream));
-        pg_launch_camera(l.stream, g, pathView(&l), c->d_band_pixels.as<uint32_t>(), l.pb, l.np, l.nl, l.sample_base,
-                         lqueue(l, l.q0.as<uint32_t>(), l.counters.as<uint32_t>()), bands);
+        if (!fuseCamera)
+            pg_launch_camera(l.stream, g, pathView(&l), c->d_band_pixels.as<uint32_t>(), l.pb, l.np, l.nl, l.sample_base,
+                             lqueue(l, l.q0.as<uint32_t>(), l.counters.as<uint32_t>()), bands);
         return launchTrace(l, nullptr, nullptr);
     };
     // film + record commit (in chunk order across lanes), statistics copy; then the next chunk
@@ -780,6 +788,8 @@ pg_status renderPass(Ctx *c, uint32_t spp, uint32_t sample_offset, int32_t recor
         const uint32_t tailMax = c->cfg.tail_paths < 0 ? 0u : c->cfg.tail_paths > 0 ? (uint32_t)c->cfg.tail_paths : tailPaths();
         const bool tail = nlive > 0 && nlive <= tailMax && l.b < maxBounces;
         if (tail) {  // one launch finishes every remaining path (shading starts at the hits just traced)
+            // straight after the camera rays it walks the camera queue, which the fused first launch did not store
+            if (l.b == 1 && fuseCamera) pg_launch_camera_queue(l.stream, l.np, l.nl, traceQueue(l, 0));
             pg_launch_tail(l.stream, g, sc, sd, pathView(&l), traceQueue(l, l.b - 1), l.bound,
                            l.tail_stats.as<unsigned long long>());
             c->stats.tail_launches += 1;

@@ -7,7 +7,8 @@ WRITE_SIZE is taken as-is.  Both counters are in KiB.
 
 bench.py measures the kernel roofline on a one-lane context after the timed region (the timed job
 overlaps three lanes, so per-launch durations there include other lanes' work).  That context's
-stream is the last one to launch k_trace, so the path kernels (k_trace, k_shade_all, k_rays; the
+stream is the last one to launch k_camera_trace (k_trace when the camera fusion is off), so the path kernels
+(k_camera_trace, k_trace, k_shade_all, k_rays; the
 unfused k_shade, k_shadow when fusion is off) are summarised over that stream only ("calibration"
 view) as well as over the whole run.
 usage: python tools/pmc_summary.py gpurun_out/prof_rNN profiles/rNN
@@ -19,7 +20,7 @@ import subprocess
 import sys
 from collections import defaultdict
 
-PATH_KERNELS = ("k_trace", "k_shade", "k_shadow", "k_shade_all", "k_rays", "k_vflight", "k_vvertex", "k_vnee")
+PATH_KERNELS = ("k_trace", "k_camera_trace", "k_shade", "k_shadow", "k_shade_all", "k_rays", "k_vflight", "k_vvertex", "k_vnee")
 
 
 def base_name(n):
@@ -31,9 +32,9 @@ def rows_of(path):
 
 
 def calibration_stream(rows):
-    """the stream of the last k_trace launch (surface path) or, for the volumetric wavefront, of the last
+    """the stream of the last k_trace / k_camera_trace launch (surface path; a chunk's first launch) or, for the volumetric wavefront, of the last
     k_vflight launch: bench.py's calibration context runs after the timed region"""
-    tr = [r for r in rows if base_name(r["Kernel_Name"]) == "k_trace" and "Stream_Id" in r]
+    tr = [r for r in rows if base_name(r["Kernel_Name"]) in ("k_trace", "k_camera_trace") and "Stream_Id" in r]
     if not tr:
         tr = [r for r in rows if base_name(r["Kernel_Name"]) == "k_vflight" and "Stream_Id" in r]
     if not tr:
