@@ -382,11 +382,15 @@ inline uint32_t pg_emitter_boxes(const float *positions, const uint32_t *indices
 // "Certain" (pg_ray_hits_blockers): the shortcut may say "occluded" only where the 8-wide walk says it too.  The
 // walk's leaf test of the blocker is this test bit for bit (same record, o, d, tmin, tmax), so the walk accepts the
 // blocker if it reaches its leaf, i.e. if every ancestor slot passes max(tn_x, tn_y, tn_z, tmin) <= min(tf_x, tf_y,
-// tf_z, tmax) with tn_a = fma(q, 2^e idir_a, (p_a - o_a) idir_a) (pg_trace.h traverseWide; no padding).  The planes
-// X = p + q 2^e are rounded outward, so they enclose the triangle; q 2^e idir is exact, and the three roundings of
-// idir, (p - o) and their product displace a computed plane by at most d_pos = 2^-21 E along its axis, E = the
-// scene's largest |coordinate| + max |o_i| (an origin inside the scene: |p - o|, |X - o| <= E).  In t that is
-// d_pos / |d_a|.  The margins below make the exact hit point P clear every such displaced plane:
+// tf_z, tmax) with tn_a = fma(q, 2^e idir_a, fma(p_a, idir_a, -(o_a idir_a)) - pad_a) and tf_a the same + pad_a,
+// pad_a = 2^-21 (|o_a idir_a| + |p_a idir_a| + 256 |2^e idir_a|) (pg_trace.h traverseWide, wideRay).  The planes
+// X = p + q 2^e are rounded outward, so they enclose the triangle; q 2^e idir is exact, and the roundings of idir,
+// o idir, the padded addends and the fmas displace a computed plane by at most 5 * 2^-24 of those three terms, i.e.
+// by less than d_pos = 2^-21 E along its axis, E = the scene's largest |coordinate| + max |o_i| (an origin inside
+// the scene: |p|, |o|, |X - o| <= E).  In t that is d_pos / |d_a|.  The pad is larger than these roundings and
+// moves the near plane earlier and the far plane later only, so it never closes a slot that the exact planes leave
+// open: "blocker says occluded => walk says occluded" holds as it did for the unpadded walk this derivation was
+// first written for, whose margins are kept.  They make the exact hit point P clear every plane displaced by d_pos:
 //   - barycentrics u, v, 1 - u - v >= 2^-10.  TriAccel's own t carries at most 2^-22 E / |den| of cancellation
 //     (den = d.n / n_k), with |den| >= max|d| / 16 below that moves the point by <= 2^-18 E and, for a triangle whose
 //     box is at least E / 32 wide on both axes other than k (rec[11], set by the host: pg_blocker_record), its
@@ -400,8 +404,8 @@ inline uint32_t pg_emitter_boxes(const float *positions, const uint32_t *indices
 //     (d_pos / |d_k| + the error of t) <= 1.5 * 2^-17 E / max|d| <= 2^-10 tmax / 2.6, inside [tmin, tmax].  (The shrink
 //     is absolute at both ends: tmin is only 1e-4 of the origin, so a shrink relative to tmin would be far less than a
 //     plane's rounding.)
-//   - every |d_a| > 1e-30: the walk replaces a zero component by +-1e-30 and picks near / far by d_a < 0, which
-//     for -0.0 disagree -- such a ray is left to the walk.
+//   - every |d_a| > 1e-30: the walk replaces a smaller component by +-1e-30 (and picks near / far by the sign of
+//     that reciprocal, -0.0 included) -- such a ray is left to the walk.
 // A ray that fails any margin is queued and walked as before.  The margins cost a negligible share of the culls.
 // Only every PG_BLOCKER_SAMPLE-th row (a block's share of a queue shard) is counted, with the number of shadow rays in those rows as
 // the total the shares refer to: a few triangles take nearly all the counts, and one add per wave and triangle on so
@@ -531,8 +535,9 @@ inline uint32_t pg_select_blockers(const uint32_t *counts, uint32_t n, uint64_t 
 // addend, both fmas and the last subtraction displace a plane by at most 6 * 2^-24 E < d_pos = 2^-21 E along its axis
 // (E as for the blockers: |origin|, |X - o| <= E to first order).  Its paddings (2^-21 |o_a|, 2^-22 |origin_a|) only
 // move the near plane earlier and the far plane later, and (1 + 2^-21) only loosens the comparison where cmax > 0.
-// The unpadded 8-wide walk of the blockers' derivation is therefore the stricter of the two, and the same margins
-// hold: barycentrics >= 2^-10 on a triangle at least E / 32 wide off its axis k (the hit point is >= 2^-16 E inside
+// The 8-wide walk of the blockers' derivation pads the same way (its planes by 2^-21 of |o_a idir_a|, |origin_a
+// idir_a| and the node's width, without the relative (1 + 2^-21)); the margins were derived for planes displaced by
+// d_pos with no padding at all, the stricter case for either walk, and the same margins hold: barycentrics >= 2^-10 on a triangle at least E / 32 wide off its axis k (the hit point is >= 2^-16 E inside
 // the box on both wide axes, 2 d_pos between them, 17 d_pos against the flat axis), |d_k|, |den| >= max|d| / 16, no
 // |d_a| <= 1e-30.  What changes is the interval: there is no tmax, so the blockers' shrink 2^-10 tmax with tmax max|d|
 // >= E / 32 becomes its smallest admissible value, t >= tmin + 2^-15 E / max|d|: the flat axis' far plane is computed at

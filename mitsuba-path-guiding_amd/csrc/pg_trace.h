@@ -148,6 +148,37 @@ __device__ __forceinline__ uint32_t permuteXor8(uint32_t m, uint32_t x) {
     return m;
 }
 
+// Per-ray slab-test setup of the 8-wide walk.  A slot's plane X = p + q 2^e is met at t = fma(q, 2^e idir, b) with
+// b = fma(p, idir, add) and add = -(o idir) per axis.  Computed so, t is off its exact value by at most about
+// 2^-24 (5 |o idir| + 4 |p idir| + 5 |q 2^e idir|): the roundings of idir (relative to t), of o idir (twice: the
+// product and the padded addend), of both fmas and of the pad's own fma.  The walk therefore moves every near plane
+// earlier and every far plane later by kWidePad (|o idir| + |p idir| + 256 |2^e idir|) on its axis, q <= 255: the
+// ray's share once per ray (addN / addF), the node's once per node, both folded into b, so a slot's test costs what
+// it did.  Without the pad a ray through a box edge far from the origin could see the rounded interval come out
+// empty and walk past the triangle inside: 26 of 91 000 occluded rays on a strip of triangles spanning 1 to 1.6e5
+// (tests/test_bvh8_build.py), i.e. light leaking through 2 shadow rays in 10 000.  The pad only widens the set of
+// slots opened, so whatever an unpadded walk would have accepted is still accepted (pg_layout.h "Shadow blockers").
+// Near and far are told apart by the sign of idir, not of d: for d_a = -0.0 (the negated axis of a directional
+// emitter) idir_a is -1e30, and picking the lo plane as the near one made every such ray walk free.
+struct WideRay {
+    f3 idir, addN, addF;
+    uint32_t octinv;  // 7 - octant: bit a set where idir is non-negative along axis a
+};
+constexpr float kWidePad = 4.76837158e-7f;  // 2^-21
+__device__ __forceinline__ WideRay wideRay(f3 o, f3 d) {
+#pragma clang fp contract(off)
+    const float eps = 1e-30f;
+    WideRay r;
+    r.idir = mk(1.0f / (fabsf(d.x) > eps ? d.x : copysignf(eps, d.x)), 1.0f / (fabsf(d.y) > eps ? d.y : copysignf(eps, d.y)),
+                1.0f / (fabsf(d.z) > eps ? d.z : copysignf(eps, d.z)));
+    r.octinv = (r.idir.x < 0 ? 0u : 1u) | (r.idir.y < 0 ? 0u : 2u) | (r.idir.z < 0 ? 0u : 4u);
+    const float ox = o.x * r.idir.x, oy = o.y * r.idir.y, oz = o.z * r.idir.z;
+    const float sx = kWidePad * fabsf(ox), sy = kWidePad * fabsf(oy), sz = kWidePad * fabsf(oz);
+    r.addN = mk(-ox - sx, -oy - sy, -oz - sz);
+    r.addF = mk(-ox + sx, -oy + sy, -oz + sz);
+    return r;
+}
+
 // Leaf triangles are taken two at a time with both first rows loaded before either test (the tests, and so the
 // accepted hit, stay in triangle order): closest hits (leafTest) k_rays 22.1 against 22.5 ms per calibration pass,
 // C3 634-635 against 625-626 Mpaths/s (profiles/r06_leafpairs/); three / four per step: k_rays 22.13 / 22.42 against
@@ -158,17 +189,16 @@ __device__ __forceinline__ uint32_t permuteXor8(uint32_t m, uint32_t x) {
 // G = (child_base, hit bits 24..31 in octant order | imask bits 0..7) and triangle group
 // T = (tri_base, hit bits 0..23); one node is opened per step, its remaining siblings stay on the
 // stack as one group entry.  (Postponing triangle groups while few lanes have triangle work, as
-// in the paper, measured slower here: 20.0 vs 17.4 ms per pass.)
+// in the paper, measured slower here: 20.0 vs 17.4 ms per pass.)  The slab test is padded outward (wideRay), so
+// an "occluded" of brute force over the triangle records is never walked past; tests/csrc/bvh_shim.cpp restates
+// this walk's arithmetic on the CPU, keep the two in step.
 template <bool ANY>
 __device__ __forceinline__ bool traverseWide(const float4 *__restrict__ nodes, const float4 *__restrict__ tris, f3 o,
                                              f3 d, float tmin, float &tmax, uint32_t &hitTri, float &hu, float &hv,
                                              const WStack &stk) {
-    const float eps = 1e-30f;
-    const f3 idir = mk(1.0f / (fabsf(d.x) > eps ? d.x : copysignf(eps, d.x)),
-                       1.0f / (fabsf(d.y) > eps ? d.y : copysignf(eps, d.y)),
-                       1.0f / (fabsf(d.z) > eps ? d.z : copysignf(eps, d.z)));
-    // 7 - octant: bit a set where the direction is non-negative along axis a
-    const uint32_t octinv = (d.x < 0 ? 0u : 1u) | (d.y < 0 ? 0u : 2u) | (d.z < 0 ? 0u : 4u);
+    const WideRay wr = wideRay(o, d);
+    const f3 idir = wr.idir, aN = wr.addN, aF = wr.addF;
+    const uint32_t octinv = wr.octinv;
     uint2 G = make_uint2(0u, 0x80000000u);  // the root, as a one-node group
     uint2 T = make_uint2(0u, 0u);
     int sp = 0;
@@ -192,11 +222,19 @@ __device__ __forceinline__ bool traverseWide(const float4 *__restrict__ nodes, c
             const float4 n3 = nodes[PG_WIDE_NODE_F4 * ni + 3];
             const float4 n4 = nodes[PG_WIDE_NODE_F4 * ni + 4];
             const uint32_t e = __float_as_uint(n0.w);
-            // t = q * (2^e * idir) + (p - o) * idir per axis; the near plane of each axis is the lo
-            // byte for a non-negative direction and the hi byte otherwise (chosen once per node)
-            const float ax = __uint_as_float((e & 0xFFu) << 23) * idir.x, bx = (n0.x - o.x) * idir.x;
-            const float ay = __uint_as_float(((e >> 8) & 0xFFu) << 23) * idir.y, by = (n0.y - o.y) * idir.y;
-            const float az = __uint_as_float(((e >> 16) & 0xFFu) << 23) * idir.z, bz = (n0.z - o.z) * idir.z;
+            // t = q * (2^e * idir) + (p * idir - o * idir) per axis; the near plane of each axis is the lo
+            // byte for a non-negative idir and the hi byte otherwise (chosen once per node).  The near planes'
+            // addend is earlier and the far planes' later by the pad (wideRay): the ray's share is in aN / aF,
+            // the node's is kWidePad (|p idir| + 256 |2^e idir|)
+            const float ax = __uint_as_float((e & 0xFFu) << 23) * idir.x;
+            const float ay = __uint_as_float(((e >> 8) & 0xFFu) << 23) * idir.y;
+            const float az = __uint_as_float(((e >> 16) & 0xFFu) << 23) * idir.z;
+            const float gx = fmaf(256.0f, fabsf(ax), fabsf(n0.x * idir.x));
+            const float gy = fmaf(256.0f, fabsf(ay), fabsf(n0.y * idir.y));
+            const float gz = fmaf(256.0f, fabsf(az), fabsf(n0.z * idir.z));
+            const float bnx = fmaf(-kWidePad, gx, fmaf(n0.x, idir.x, aN.x)), bfx = fmaf(kWidePad, gx, fmaf(n0.x, idir.x, aF.x));
+            const float bny = fmaf(-kWidePad, gy, fmaf(n0.y, idir.y, aN.y)), bfy = fmaf(kWidePad, gy, fmaf(n0.y, idir.y, aF.y));
+            const float bnz = fmaf(-kWidePad, gz, fmaf(n0.z, idir.z, aN.z)), bfz = fmaf(kWidePad, gz, fmaf(n0.z, idir.z, aF.z));
             const uint32_t imask = e >> 24;
             const bool px = octinv & 1u, py = octinv & 2u, pz = octinv & 4u;
             const uint32_t loX0 = __float_as_uint(n2.x), loX1 = __float_as_uint(n2.y);
@@ -211,9 +249,9 @@ __device__ __forceinline__ bool traverseWide(const float4 *__restrict__ nodes, c
             uint32_t hitSlots = 0;
 #pragma unroll
             for (int s = 0; s < 8; ++s) {
-                const float tnx = fmaf(qbyte(nX0, nX1, s), ax, bx), tfx = fmaf(qbyte(fX0, fX1, s), ax, bx);
-                const float tny = fmaf(qbyte(nY0, nY1, s), ay, by), tfy = fmaf(qbyte(fY0, fY1, s), ay, by);
-                const float tnz = fmaf(qbyte(nZ0, nZ1, s), az, bz), tfz = fmaf(qbyte(fZ0, fZ1, s), az, bz);
+                const float tnx = fmaf(qbyte(nX0, nX1, s), ax, bnx), tfx = fmaf(qbyte(fX0, fX1, s), ax, bfx);
+                const float tny = fmaf(qbyte(nY0, nY1, s), ay, bny), tfy = fmaf(qbyte(fY0, fY1, s), ay, bfy);
+                const float tnz = fmaf(qbyte(nZ0, nZ1, s), az, bnz), tfz = fmaf(qbyte(fZ0, fZ1, s), az, bfz);
                 const float cmin = max3f(tnx, tny, fmaxf(tnz, tmin));
                 const float cmax = min3f(tfx, tfy, fminf(tfz, tmax));
                 hitSlots |= (cmin <= cmax ? 1u : 0u) << s;

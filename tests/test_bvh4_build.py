@@ -40,6 +40,8 @@ def build_shim(tmp_path_factory, fma=False):
     L.shim_check.argtypes = [C.c_uint32, C.c_void_p]
     L.shim_trace.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]
     L.shim_order.argtypes = [C.c_void_p]
+    L.shim_check_wide.argtypes = [C.c_uint32, C.c_void_p]  # the 8-wide tree: tests/test_bvh8_build.py
+    L.shim_trace_any.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]
     return L
 
 
@@ -116,7 +118,8 @@ def geometry(pg, name):
     return sc.positions.reshape(-1, 3), sc.indices.reshape(-1, 3)
 
 
-def rays_through(V, F, n, seed):
+def rays_through(V, F, n, seed, targets=False):
+    """targets: also return the centroids the directions were aimed at (from the origins on the sphere)"""
     rng = np.random.default_rng(seed)
     lo, hi = V.min(0), V.max(0)
     ctr, rad = (lo + hi) / 2, np.linalg.norm(hi - lo) / 2 + 1e-3
@@ -128,7 +131,7 @@ def rays_through(V, F, n, seed):
     a[inner] = (lo + (hi - lo) * rng.random((n, 3)))[inner]
     r = np.zeros((n, 8), np.float32)
     r[:, 0:3], r[:, 3], r[:, 4:7], r[:, 7] = a, 1e-5, d, np.inf
-    return r
+    return (r, b) if targets else r
 
 
 @pytest.mark.parametrize("name", ["ajar", "cornell", "bunny", "strip", "dups", "single"])

@@ -132,6 +132,49 @@ def test_trace_matches_bruteforce(pg, O, tmp_path_factory, name):
     np.testing.assert_array_equal(g[hit][:, [0, 2, 3]], cpu[hit][:, [0, 2, 3]])
 
 
+@pytest.mark.parametrize("name", ["strip", "bunny", "dups"])
+def test_any_hit_matches_bruteforce(pg, O, tmp_path_factory, name):
+    """GPU shadow rays (pg_trace_rays(any_hit = 1), the 8-wide walk traverseWide<true>) against brute force over the
+    library's own triangle records on the CPU (tests/csrc/bvh_shim.cpp shim_trace_any) and against the oracle, on the
+    ray families of test_bvh8_build: rays through the scene with tmax = inf, the same with a finite tmax,
+    surface-to-surface segments with the shadow rays' epsilons, and axis-parallel rays (zero direction components
+    of both signs).  Exact both ways: where the walk says occluded, brute force accepts a triangle; where brute force
+    accepts a triangle at a t inside that triangle's own box, the walk says occluded.  The strip's 100 000 rays per
+    family are what it takes to see the 2-in-10 000 misses of the unpadded slab test (pg_trace.h wideRay)."""
+    import test_bvh4_build as T
+    import test_bvh8_build as W
+    shim = T.build_shim(tmp_path_factory)
+    V, F, fams = W.references(pg, shim, name, 100_000 if name == "strip" else 4000)
+    s = pg.scenes.Scene()
+    s.add_mesh(V, F, material=s.add_material(pg.scenes.material("diffuse")))
+    c = V.mean(0)
+    s.set_camera(tuple(c + np.array([0, 0, 1.0])), tuple(c), (0, 1, 0), 40, 8, 8)
+    s.finalize()
+    dev = make_dev(pg, s)
+    occ = {fam: dev.trace_rays(rays, any_hit=True)[:, 0] > 0.5 for fam, (rays, _, _) in fams.items()}
+    dev.close()
+    osc = O.OracleScene(pg.capi, s)
+    failed = []
+    for fam, (rays, walk, brute) in fams.items():
+        hit, consistent = brute[:, 0] > 0, brute[:, 1] == 1
+        try:  # the device returns 0 / 1 only: a false positive is an "occluded" where brute force accepts nothing
+            W.check_family(f"gpu {name}/{fam}", occ[fam], brute, hit)
+        except AssertionError as e:  # every family's figures are printed before the test fails
+            failed.append(str(e))
+        # the walk's CPU restatement is the device's arithmetic: the same answers, excluded rays included
+        same = int((occ[fam] == (walk != 0xFFFFFFFF)).sum())
+        print(f"gpu {name}/{fam}: {same} of {len(walk)} answers equal the CPU restatement's")
+        if same != len(walk):
+            failed.append(f"gpu {name}/{fam}: {len(walk) - same} answers differ from the CPU restatement's")
+        # the oracle (its own BVH and slab test) on every ray that is not excluded
+        keep = ~(hit & ~consistent)
+        oc = osc.trace(rays, any_hit=True)[:, 0] > 0.5
+        diff = int((occ[fam] != oc)[keep].sum())
+        if diff:
+            failed.append(f"gpu {name}/{fam}: {diff} answers differ from the oracle's")
+    assert not failed, failed
+
+
 def test_dgeom_kat_gpu(pg, O):
     """src/tests/test_dgeom.cpp:35-177 through the GPU traversal and the shading kernels' hit record
     (pg_hit_records: fetchHit's position, geometric and shading normals, shading frame and local wi), and
