@@ -1,5 +1,5 @@
 // Host-side BVH builders producing the GPU layouts of pg_layout.h from one binned-SAH binary build
-// (leaves <= 3 triangles): a 4-wide BVH (64-B nodes) for closest-hit rays, and an 8-wide BVH with
+// (leaves <= 3 triangles), reoptimised by subtree reinsertion above its leaves (PG_BVH_REINSERT=0: as built): a 4-wide BVH (64-B nodes) for closest-hit rays, and an 8-wide BVH with
 // quantised child boxes (80-B nodes, collapsed SAH-optimally from the same tree) for shadow rays,
 // which it traverses with 28 % less time.  Both index one array of 48-B triangle records (pg_layout.h "Triangle records").  Replaces the reference's SAH kd-tree build
 // (include/mitsuba/render/sahkdtree3.h, gkdtree.h) — only the closest-hit contract is kept.
@@ -22,6 +22,7 @@ struct BvhOut {
     std::vector<float> wnodes;
     uint32_t wide_depth = 0;
     float lo[3], hi[3];
+    float sah_cost = 0.0f;        // SAH cost of the binary tree both were collapsed from, relative to the root's area
 };
 
 // positions: 3*nv floats, indices: 3*nt.  Returns false if either tree is deeper than
