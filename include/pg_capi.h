@@ -388,6 +388,55 @@ pg_status pg_rfilter_table(int32_t type, float param, float *radius_out, float *
  * PG_ERR_STATE when no filter is set.  pg_reset_film clears it; pg_comm_reduce_film sums it (int64, exact). */
 pg_status pg_set_rfilter(void *ctx, float radius, const float *values /* [32] or NULL */);
 pg_status pg_read_film_filtered(void *ctx, float *rgbw, int64_t *raw);
+/* ---- denoiser: the library's own filter over the film and the feature buffers ----------------------------------
+ * New entry points; pg_config, pg_stats and PG_ABI_VERSION are unchanged.  While none of them is called, nothing
+ * below is allocated or launched and every other result is bit for bit what it was.
+ *
+ * The reference hands colour, albedo and normal to OIDN (Denoiser::denoise, src/librender/denoiser.cpp); OIDN is a
+ * neural network and stays with the Mitsuba adapter.  This is an edge-avoiding a-trous wavelet (Dammertz et al.
+ * 2010) steered by the albedo and normal sums and by the per-pixel variance of the mean, as the spatial part of
+ * SVGF is (Schied et al. 2017).  The reference has no such filter: what follows is its definition, restated in
+ * float64 by tests/denoise_ref.py.  float32 on the device, no FP contraction.
+ *
+ * Per pixel: rgbw = (sum L, n), sumsq = (sum L^2, 0), albedo = (sum a, n), normal = (sum N, 0); n is rgbw's.
+ * 1. A pixel with n = 0 is invalid: its output is 0 and it is no tap of any pixel.  Otherwise c = sum L / n,
+ *    abar = sum a / n, N = sum N / n normalised (0 if its length is 0), mod = abar + 0.01 per channel, and the
+ *    filtered quantity is e = c / mod.  Variance of the mean per channel: max(sum L^2 / n - c^2, 0) / n for n >= 2,
+ *    c^2 for n < 2; V = lum(var / mod^2), lum = 0.2126 r + 0.7152 g + 0.0722 b.
+ * 2. Level i = 0 .. levels - 1, step s = 2^i, from (e, V) to (e', V'), with the distances between pixels p and q
+ *    d_n = max(0, 1 - N_p . N_q) / sigma_n and d_a = |abar_p - abar_q|^2 / sigma_a^2:
+ *    (a) Vt_p = the 3 x 3 average of V at step 1 with weights (1/4, 1/2, 1/4)^2 over the taps inside the image,
+ *        valid and with d_n + d_a <= 80, divided by the sum of the weights used; the centre always counts.
+ *    (b) taps q = p + s (dx, dy), dx, dy = -2 .. 2, h = (1/16, 1/4, 3/8, 1/4, 1/16):
+ *        d = d_n + d_a + |lum(e_p) - lum(e_q)| / (sigma_l sqrt(Vt_p) + 1e-6); a tap outside the image, an invalid
+ *        tap or one with d > 80 has weight 0 (a hard cut: a feature edge is impermeable), any other
+ *        w = h(dx) h(dy) exp(-d), the centre h(0)^2 unconditionally; e'_p = sum w e_q / sum w (accumulated as
+ *        e_p + sum w (e_q - e_p) / sum w), V'_p = sum w^2 V_q / (sum w)^2.
+ * 3. Output (e mod).rgb and the last V; invalid pixels give four zeros.
+ * No atomics and no order dependence: two runs give the same bits. */
+typedef struct pg_denoise_params {
+    int32_t levels;  /* 1..6; 5 */
+    float sigma_l;   /* > 0; 4.0 */
+    float sigma_n;   /* > 0; 0.1 */
+    float sigma_a;   /* > 0; 0.1 */
+} pg_denoise_params;
+/* The defaults.  Needs no device or context. */
+pg_status pg_denoise_default_params(pg_denoise_params *params);
+/* Filters the context's own film, sumsq and feature buffers where they lie and copies width * height * 4 floats
+ * out (r, g, b, V).  params == NULL: the defaults.  PG_ERR_STATE without a scene or with pg_config.aovs = 0;
+ * PG_ERR_INVALID for parameters out of range or not finite.  The film, sumsq and feature buffers are left as they
+ * are; the scratch (four rows of 16 bytes per pixel) is allocated by the first call and freed with the context.  On
+ * the root rank after pg_comm_reduce_film this is the whole image; on any other rank, its own tiles. */
+pg_status pg_denoise(void *ctx, const pg_denoise_params *params, float *out_rgbv);
+/* The same kernels on host arrays of width x height pixels (1 <= width, height <= 65536, at most 2^28 pixels) in the
+ * layouts above: combined or reloaded images.  Any context works, with or without a scene or feature buffers; nothing
+ * of the context changes.  PG_ERR_INVALID: a null array, a zero or oversized image, parameters as above. */
+pg_status pg_denoise_arrays(void *ctx, const pg_denoise_params *params, uint32_t width, uint32_t height,
+                            const float *rgbw, const float *sumsq, const float *albedo, const float *normal,
+                            float *out_rgbv);
+/* Device time of the last pg_denoise / pg_denoise_arrays of this context in milliseconds, from events around its
+ * kernel launches (no copies).  PG_ERR_STATE before the first. */
+pg_status pg_denoise_time(void *ctx, float *ms_out);
 /* ---- textures: a bitmap or a checkerboard as the diffuse reflectance of a material ------------------------------
  * New entry points; pg_config, pg_stats, pg_scene_desc, pg_material and PG_ABI_VERSION are unchanged.  While no
  * texture is bound, no texture buffer is allocated on the device, no kernel compiled for textures is launched and

@@ -123,6 +123,14 @@ class pg_record(C.Structure):
                 ("product", C.c_float), ("weight", C.c_float)]
 
 
+class pg_denoise_params(C.Structure):
+    """pg_denoise / pg_denoise_arrays: a-trous levels (1..6) and the luminance, normal and albedo tolerances (> 0)"""
+    _fields_ = [("levels", C.c_int32), ("sigma_l", C.c_float), ("sigma_n", C.c_float), ("sigma_a", C.c_float)]
+
+    def __init__(self, levels=5, sigma_l=4.0, sigma_n=0.1, sigma_a=0.1):
+        super().__init__(levels, sigma_l, sigma_n, sigma_a)
+
+
 class pg_stats(C.Structure):
     _fields_ = [("paths", C.c_uint64), ("segments", C.c_uint64), ("shadow_rays", C.c_uint64), ("records", C.c_uint64),
                 ("trace_ms", C.c_double), ("shade_ms", C.c_double), ("shadow_ms", C.c_double), ("other_ms", C.c_double),
@@ -203,6 +211,10 @@ SIGNATURES = [
     ("pg_rfilter_table", C.c_int32, [C.c_int32, C.c_float, C.POINTER(C.c_float), VP]),
     ("pg_set_rfilter", C.c_int32, [VP, C.c_float, VP]),
     ("pg_read_film_filtered", C.c_int32, [VP, VP, VP]),
+    ("pg_denoise_default_params", C.c_int32, [C.POINTER(pg_denoise_params)]),
+    ("pg_denoise", C.c_int32, [VP, C.POINTER(pg_denoise_params), VP]),
+    ("pg_denoise_arrays", C.c_int32, [VP, C.POINTER(pg_denoise_params), C.c_uint32, C.c_uint32, VP, VP, VP, VP, VP]),
+    ("pg_denoise_time", C.c_int32, [VP, C.POINTER(C.c_float)]),
     ("pg_set_textures", C.c_int32, [VP, C.POINTER(pg_texture), C.c_uint32, C.POINTER(pg_texture_binding), C.c_uint32, VP]),
     ("pg_texture_query", C.c_int32, [VP, C.POINTER(pg_texture), VP, C.c_uint64, VP]),
     ("pg_hit_uvs", C.c_int32, [VP, VP, C.c_uint64, VP]),

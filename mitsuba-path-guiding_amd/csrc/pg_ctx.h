@@ -235,6 +235,10 @@ struct Ctx {
     DevBuf film_acc, filter_tab, tile_first, tile_origin;
     std::vector<uint32_t> h_tile_first;  // local tile k = local pixels [h_tile_first[k], h_tile_first[k + 1])
     std::vector<uint32_t> h_tile_origin; // (x, y) pairs
+    // denoiser (pg_denoise): nothing is allocated or created before the first call
+    DevBuf dn_scratch;                  // pg_denoise's four rows per pixel: ev ping, ev pong, fn, fa
+    EventPair dn_ev;                    // around the last call's launches (pg_denoise_time)
+    bool dn_timed = false;
     // records
     DevBuf records, rec_count;
     uint64_t rec_capacity = 0;

@@ -266,6 +266,15 @@ inline size_t pg_film_filter_lds_bytes(uint32_t tile, int32_t border) {
 void pg_launch_film_filtered(hipStream_t s, const GParams &g, const SceneDev &sc, const PathDev &p, const FilmFilter &f,
                              const uint32_t *local_pixels, uint32_t pix_begin, uint32_t npix, uint32_t nlayers,
                              uint32_t sample_base, uint32_t tile0, uint32_t ntiles);
+// Film denoiser (pg_denoise, pg_denoise_arrays; pg_denoise.hip).  prepare: the film and feature sums of
+// width * height pixels -> ev = (e.rgb, V), fn = (N.xyz, valid), fa = (albedo mean, 0).  level: one a-trous level
+// at `step` from ev into out (another buffer); the last level multiplies the modulation back.  tiled: steps 1 and 2
+// read their taps from an LDS tile (same bits as the gather).
+void pg_launch_denoise_prepare(hipStream_t s, uint32_t width, uint32_t height, const float4 *rgbw, const float4 *sumsq,
+                               const float4 *albedo, const float4 *normal, float4 *ev, float4 *fn, float4 *fa);
+void pg_launch_denoise_level(hipStream_t s, uint32_t width, uint32_t height, int step, float sigma_l, float sigma_n,
+                             float sigma_a, bool last, const float4 *ev, const float4 *fn, const float4 *fa,
+                             float4 *out, bool tiled);
 // unit-level environment-emitter queries (pg_envmap_query)
 void pg_launch_envmap_query(hipStream_t s, const SceneDev &sc, int op, const float *in, uint32_t n, float *out);
 // unit-level emitter sampling (pg_emitter_query): sampleEmitter over area, delta and environment emitters at ref

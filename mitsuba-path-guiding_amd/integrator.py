@@ -82,6 +82,15 @@ def rfilter_table(name, stddev=0.5):
     return radius.value, values
 
 
+def _denoise_params(params):
+    """None (the library's defaults), a capi.pg_denoise_params or a dict of its fields -> the ctypes argument"""
+    if params is None:
+        return None
+    if isinstance(params, dict):
+        params = capi.pg_denoise_params(**params)
+    return C.byref(params)
+
+
 def develop(rgbw):
     """hdrfilm's division by the weight channel: sum w L / sum w per pixel, 0 where sum w = 0; (H, W, 3)."""
     w = rgbw[..., 3:4]
@@ -379,6 +388,32 @@ class Device:
         self._chk(self.lib.pg_read_aovs(self.h, _p(alb), _p(nrm)))
         return alb, nrm
 
+    def denoise(self, params=None):
+        """pg_denoise: the library's a-trous filter over this context's film and feature buffers (pg_config.aovs = 1),
+        (H, W, 4): r, g, b and the filtered variance.  params: a capi.pg_denoise_params, a dict of its fields, or
+        None for the defaults."""
+        W, H = self.scene.width, self.scene.height
+        out = np.zeros((H, W, 4), np.float32)
+        self._chk(self.lib.pg_denoise(self.h, _denoise_params(params), _p(out)))
+        return out
+
+    def denoise_arrays(self, rgbw, sumsq, albedo, normal, params=None):
+        """pg_denoise_arrays: the same filter on host arrays (H, W, 4) in the film's and the feature buffers'
+        layouts; needs neither a scene nor aovs."""
+        arrs = [np.ascontiguousarray(a, np.float32) for a in (rgbw, sumsq, albedo, normal)]
+        if arrs[0].ndim != 3 or arrs[0].shape[2] != 4 or any(a.shape != arrs[0].shape for a in arrs):
+            raise ValueError("denoise_arrays: four arrays of one shape (H, W, 4)")
+        H, W = arrs[0].shape[:2]
+        out = np.zeros((H, W, 4), np.float32)
+        self._chk(self.lib.pg_denoise_arrays(self.h, _denoise_params(params), W, H, *(_p(a) for a in arrs), _p(out)))
+        return out
+
+    def denoise_ms(self):
+        """Device time of the last denoise / denoise_arrays in ms (pg_denoise_time: events around the launches)."""
+        ms = C.c_float()
+        self._chk(self.lib.pg_denoise_time(self.h, C.byref(ms)))
+        return ms.value
+
     def stats(self):
         s = capi.pg_stats()
         self._chk(self.lib.pg_get_stats(self.h, C.byref(s)))
@@ -480,6 +515,17 @@ class ProgressivePathTracer:
         # callable(np.float64 array) -> its element-wise sum over ranks (world_size > 1): maxRenderTime's
         # progression agreement, inverse-variance weights over the whole image
         self.reduce_sum = reduce_sum
+        # denoise: the library's own filter (pg_denoise) over the film and the feature buffers after render(), which
+        # then leaves `denoised` (H, W, 3) and `denoised_variance` (H, W); implies aovs.  denoiseLevels (1..6),
+        # denoiseSigmaL / denoiseSigmaN / denoiseSigmaA: pg_denoise_params.
+        self.denoise = bool(props.get("denoise", False))
+        if self.denoise and self.integrator != capi.PG_INTEGRATOR_PATH:
+            raise ValueError("denoise needs the feature buffers (aovs), which the volumetric integrator does not have")
+        self.denoise_params = capi.pg_denoise_params(
+            levels=int(props.get("denoiseLevels", 5)), sigma_l=float(props.get("denoiseSigmaL", 4.0)),
+            sigma_n=float(props.get("denoiseSigmaN", 0.1)), sigma_a=float(props.get("denoiseSigmaA", 0.1)))
+        self.denoised = None
+        self.denoised_variance = None
         self.cfg = capi.default_config(
             device=device, rank=rank, world_size=world_size,
             max_depth=int(props.get("maxDepth", -1)), rr_depth=int(props.get("rrDepth", 5)),
@@ -494,7 +540,7 @@ class ProgressivePathTracer:
             max_paths_in_flight=int(props.get("maxPathsInFlight", 0)), integrator=self.integrator,
             path_lanes=int(props.get("pathLanes", 0)),
             distance_guiding=float(props.get("distanceGuiding", 0.25)),
-            aovs=int(bool(props.get("aovs", False))),
+            aovs=int(bool(props.get("aovs", False)) or self.denoise),
             volpath_exact_mis=int(bool(props.get("exactMis", False))),
             tail_paths=int(props.get("tailPaths", 0)),
             glossy_prior=int(bool(props.get("glossyPrior", False))),
@@ -582,12 +628,17 @@ class ProgressivePathTracer:
         rgbw, sq = self.dev.read_film()
         if self.rfilter is not None:
             self.filtered = self.dev.read_film_filtered()
+        den = self.dev.denoise(self.denoise_params) if self.denoise else None
         if getattr(self.dev.scene, "mirror_x", False):  # a mirrored sensor (e.g. <scale x="-1"/> in toWorld)
             rgbw, sq = rgbw[:, ::-1].copy(), sq[:, ::-1].copy()
+            if den is not None:
+                den = den[:, ::-1].copy()
             if self.filtered is not None:
                 self.filtered = self.filtered[:, ::-1].copy()
         if self.filtered is not None:
             self.developed = develop(self.filtered)
+        if den is not None:
+            self.denoised, self.denoised_variance = den[..., :3].copy(), den[..., 3].copy()
         return rgbw, sq
 
     def _render_time_sharded(self, t0):
@@ -679,6 +730,9 @@ class GuidedPathTracer(ProgressivePathTracer):
         self.sample_combination = str(self.props.get("sampleCombination", "discard")).lower()
         if self.sample_combination not in ("discard", "inversevar"):
             raise ValueError(f"sampleCombination must be discard or inversevar, not {self.sample_combination!r}")
+        if self.denoise and self.sample_combination == "inversevar":
+            raise ValueError("denoise cannot follow sampleCombination = inversevar: the combined sums carry no valid "
+                             "variance of the mean")
         self.iteration_films = []
         self.combination_weights = None
 
