@@ -465,7 +465,7 @@ pg_status pg_denoise_time(void *ctx, float *ms_out);
  * (Texture::getAverage, plastic.cpp:201-202): `average`, or where average[0] < 0 the mean of the texels / (color0 +
  * color1) / 2.  Deviations from the reference: filterType ewa and trilinear are to be passed as bilinear (the
  * reference filters camera-ray hits with the ray differentials; every later vertex is level-0 bilinear there too),
- * and the shading frame keeps dpdu = p1 - p0 (no computeUVTangents). */
+ * and the shading frame keeps dpdu = p1 - p0 (computeUVTangents only for normal-mapped materials, below). */
 enum { PG_TEXTURE_BITMAP = 0, PG_TEXTURE_CHECKERBOARD = 1 };
 enum { PG_TEXFILTER_NEAREST = 0, PG_TEXFILTER_BILINEAR = 1 };
 enum { PG_TEXWRAP_REPEAT = 0, PG_TEXWRAP_CLAMP = 1, PG_TEXWRAP_MIRROR = 2, PG_TEXWRAP_ZERO = 3, PG_TEXWRAP_ONE = 4 };
@@ -501,6 +501,44 @@ pg_status pg_set_textures(void *ctx, const pg_texture *textures, uint32_t n_text
  * the texcoords of the last pg_set_textures, else the barycentrics. */
 pg_status pg_texture_query(void *ctx, const pg_texture *texture, const float *uv, uint64_t n, float *out);
 pg_status pg_hit_uvs(void *ctx, const float *rays, uint64_t n, float *out);
+/* ---- normal maps: the normalmap BSDF adapter (normalmap.cpp) on the surface integrator ---------------------------
+ * New entry points; no struct and not PG_ABI_VERSION change.  While no map is bound, no buffer of the feature is
+ * allocated, no kernel instantiation is launched that was not launched before and every result is bit for bit what
+ * it was.  All of the following is float32 in the order written, without contraction (#pragma clang fp
+ * contract(off)).
+ *   dpdu  of a triangle whose material carries a map is the tangent of TriMesh::computeUVTangents
+ *         (trimesh.cpp:683-735), computed on the host per triangle: with dP1 = p1 - p0, dP2 = p2 - p0, dUV1 = t1 - t0,
+ *         dUV2 = t2 - t0 and det = dUV1.x dUV2.y - dUV1.y dUV2.x,
+ *             dpdu = (dUV2.y dP1 - dUV1.y dP2) * (1 / det);
+ *         det == 0: the first vector of coordinateSystem(cross(dP1, dP2) / |cross(dP1, dP2)|) (util.cpp:594-603); a
+ *         zero-area triangle, and every triangle without texcoords (uv = the barycentrics, det = 1), keeps p1 - p0.
+ *         Triangles of every other material keep dpdu = p1 - p0 bit for bit.
+ *   base  = computeShadingFrame(shN, dpdu) (skdtree.h:373-380,426): n = shN, s = normalize(dpdu - n dot(n, dpdu)),
+ *         t = cross(n, s).
+ *   c     = the map's value at the hit's uv: the lookup of pg_set_textures above (uv transform, filter, wrap modes).
+ *   nl    = 2 c - 1,  n' = normalize(base.toWorld(nl)),  s' = normalize(dpdu - n' dot(n', dpdu)),  t' = cross(n', s')
+ *         (NormalMap::getFrame, normalmap.cpp:141-158).  A texel of (0.5, 0.5, 0.5) has no direction: unspecified.
+ * Every BSDF eval, pdf and sample of the vertex (next-event estimation, the BSDF sample, the guided branch's eval and
+ * pdf of the D-tree direction, the glossy sampling rate) runs in (s', t', n') with wi = toLocal'(-d).  Hemisphere rule
+ * (normalmap.cpp:215,233,258,280): a direction wo evaluates to zero, and a sampled one is rejected, when
+ * dot(wo_world, shN) * wo'.z <= 0, shN the unperturbed shading normal.  On the unperturbed frame stay: the emitter
+ * side test, the reference normal of the emitter sampling, both strict_normals tests (dot(-d, shN) and dot(wo, shN),
+ * the reference's its.wi.z and bRec.wo.z), the emitter-hit MIS pdf, the training record and the denoiser buffers.
+ * The map is the outermost adapter, normalmap{ [twosided{] bsdf [}] }: PG_MAT_TWOSIDED of the bound material flips in
+ * the perturbed frame.  (twosided{normalmap{}} mirrors about the unperturbed tangent plane: not expressible here.)
+ * Bound materials: diffuse, plastic, roughplastic, conductor, roughconductor; a material may carry a texture
+ * (pg_set_textures) and a map.  Life cycle as pg_set_textures: after pg_upload_scene and before the first render pass
+ * (PG_ERR_STATE otherwise), cleared by a later pg_upload_scene, n_bindings == 0 turns the maps off.  The texcoords
+ * belong to the scene: where this call and pg_set_textures both pass them they must be equal, and where one passes
+ * NULL it reads the other's.  PG_ERR_INVALID: as pg_set_textures for the records and indices, a dielectric,
+ * roughdielectric or null material, a material bound twice, unequal texcoords, the volumetric integrator.
+ * `average` is not read. */
+pg_status pg_set_normal_maps(void *ctx, const pg_texture *maps, uint32_t n_maps, const pg_texture_binding *bindings,
+                             uint32_t n_bindings, const float *texcoords);
+/* Unit entry point beside pg_hit_records: the frame the closest hit's BSDF calls run in (rays: n x 8 as
+ * pg_trace_rays).  out: n x 12, (n', s', t', wi'); the base frame with dpdu = p1 - p0 and its wi where the material
+ * carries no map; zeros for a miss. */
+pg_status pg_hit_frames(void *ctx, const float *rays, uint64_t n, float *out);
 /* ---- thin-lens sensor: depth of field in both integrators ---------------------------------------------------------
  * New entry points; pg_config, pg_stats, pg_scene_desc, pg_camera and PG_ABI_VERSION are unchanged.  The camera of
  * pg_scene_desc is a pinhole (PerspectiveCamera::sampleRay, perspective.cpp:271-298); pg_set_lens puts the thin lens

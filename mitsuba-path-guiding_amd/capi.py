@@ -218,6 +218,8 @@ SIGNATURES = [
     ("pg_set_textures", C.c_int32, [VP, C.POINTER(pg_texture), C.c_uint32, C.POINTER(pg_texture_binding), C.c_uint32, VP]),
     ("pg_texture_query", C.c_int32, [VP, C.POINTER(pg_texture), VP, C.c_uint64, VP]),
     ("pg_hit_uvs", C.c_int32, [VP, VP, C.c_uint64, VP]),
+    ("pg_set_normal_maps", C.c_int32, [VP, C.POINTER(pg_texture), C.c_uint32, C.POINTER(pg_texture_binding), C.c_uint32, VP]),
+    ("pg_hit_frames", C.c_int32, [VP, VP, C.c_uint64, VP]),
     ("pg_set_lens", C.c_int32, [VP, C.c_float, C.c_float]),
     ("pg_get_lens", C.c_int32, [VP, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     ("pg_camera_rays", C.c_int32, [VP, VP, VP, C.c_uint32, VP, VP]),

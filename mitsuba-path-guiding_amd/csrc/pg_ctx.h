@@ -201,6 +201,13 @@ struct Ctx {
     std::vector<uint8_t> base_tclass;
     std::vector<uint32_t> host_indices;  // the uploaded scene's triangles (their vertices' texcoords)
     uint32_t num_vertices = 0;
+    // normal maps (pg_set_normal_maps): nothing is allocated while `nmapped` is false.  The two calls share the uv
+    // records, the triangle classes and mtex (syncTexRows), so each keeps what it was given: the per-material indices
+    // (empty: off) and the texcoords (empty: none passed)
+    bool nmapped = false;
+    DevBuf ntex, mnmap, ntexels, ttan;
+    std::vector<uint32_t> host_mtex, host_mnmap;
+    std::vector<float> tex_uv, nmap_uv;
     float scene_lo[3] = {0, 0, 0}, scene_hi[3] = {0, 0, 0};
     // delta emitters (pg_set_delta_emitters): nothing is allocated while num_delta is 0.  tri_lo / tri_hi: the
     // uploaded triangles' box, whose bounding sphere a directional emitter's disk lies on

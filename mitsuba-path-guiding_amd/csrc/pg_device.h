@@ -467,15 +467,19 @@ PGD float roughPlasticProbSpec(const GMat &M, float cosThetaI) {
 // material is one of them: the surface launches drop the microfacet, dielectric and plastic code and its
 // registers, pg_volpath.hip k_vvertex KIND 3); -1 dispatches on M.model at run time
 constexpr int PG_MODELS_DIFFUSE_NULL = -2;
-// the models with a diffuse-reflectance slot (the textured material class, pg_layout.h PG_CLASS_TEXTURED)
-constexpr int PG_MODELS_DIFFUSE_SLOT = -3;
+// the models of the textured material class (pg_layout.h PG_CLASS_TEXTURED): those with a diffuse-reflectance slot
+// (pg_set_textures) and the two conductors, which a normal map may also nest (pg_set_normal_maps)
+constexpr int PG_MODELS_TEXTURED = -3;
 template <int MODEL>
 PGD int modelSel(const GMat &M) {
     if constexpr (MODEL >= 0) return MODEL;
     else if constexpr (MODEL == PG_MODELS_DIFFUSE_NULL) return M.model == PG_BSDF_NULL ? PG_BSDF_NULL : PG_BSDF_DIFFUSE;
-    else if constexpr (MODEL == PG_MODELS_DIFFUSE_SLOT)
-        return M.model == PG_BSDF_PLASTIC ? PG_BSDF_PLASTIC
-                                          : M.model == PG_BSDF_ROUGHPLASTIC ? PG_BSDF_ROUGHPLASTIC : PG_BSDF_DIFFUSE;
+    else if constexpr (MODEL == PG_MODELS_TEXTURED)
+        return M.model == PG_BSDF_PLASTIC          ? PG_BSDF_PLASTIC
+               : M.model == PG_BSDF_ROUGHPLASTIC   ? PG_BSDF_ROUGHPLASTIC
+               : M.model == PG_BSDF_CONDUCTOR      ? PG_BSDF_CONDUCTOR
+               : M.model == PG_BSDF_ROUGHCONDUCTOR ? PG_BSDF_ROUGHCONDUCTOR
+                                                   : PG_BSDF_DIFFUSE;
     else return (int)M.model;
 }
 

@@ -197,10 +197,15 @@ SceneDev sceneView(const Ctx *c) {
     sc.num_occluders = probeListEnabled(c) ? c->num_occluders : 0u;
     sc.prb_counts = sc.prb_total = nullptr;  // set by the recording passes
     std::memcpy(sc.prb, c->prb, sizeof(sc.prb));
-    if (c->textured) {
+    if (c->textured || c->nmapped) {  // syncTexRows: both calls share the uv records and mtex
         sc.tuv = c->tuv.as<float4>();
-        sc.tex = c->tex.as<GTex>();
         sc.mtex = c->mtex.as<uint32_t>();
+    }
+    if (c->textured) sc.tex = c->tex.as<GTex>();
+    if (c->nmapped) {
+        sc.ntex = c->ntex.as<GTex>();
+        sc.mnmap = c->mnmap.as<uint32_t>();
+        sc.ttan = c->ttan.as<float4>();
     }
     if (c->num_delta) sc.delta = c->delta.as<GDelta>();
     return sc;
@@ -872,15 +877,127 @@ void texAverageMax(const pg_texture &t, float avg[3], float mx[3]) {
     if (!(t.average[0] < 0))
         for (int k = 0; k < 3; ++k) avg[k] = t.average[k];
 }
-// the untextured scene's materials and triangle classes back on the device
+// TriMesh::computeUVTangents (trimesh.cpp:683-735) of one triangle, float32 without contraction: dpdu of pg_capi.h
+// "normal maps".  uv: the three vertices' texcoords, or nullptr (no texcoords: p1 - p0)
+void uvTangent(const float *p0, const float *p1, const float *p2, const float *uv, float dpdu[3]) {
+    const float d1[3] = {p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]}, d2[3] = {p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2]};
+    for (int a = 0; a < 3; ++a) dpdu[a] = d1[a];
+    if (!uv) return;
+    const float n[3] = {d1[1] * d2[2] - d1[2] * d2[1], d1[2] * d2[0] - d1[0] * d2[2], d1[0] * d2[1] - d1[1] * d2[0]};
+    const float length = std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+    if (length == 0) return;
+    const float u1[2] = {uv[2] - uv[0], uv[3] - uv[1]}, u2[2] = {uv[4] - uv[0], uv[5] - uv[1]};
+    const float det = u1[0] * u2[1] - u1[1] * u2[0];
+    if (det == 0) {  // coordinateSystem(n / length, dpdu, dpdv) (util.cpp:594-603): dpdu = cross(dpdv, a)
+        const float a[3] = {n[0] / length, n[1] / length, n[2] / length};
+        float c3[3];
+        if (std::fabs(a[0]) > std::fabs(a[1])) {
+            const float invLen = 1.0f / std::sqrt(a[0] * a[0] + a[2] * a[2]);
+            c3[0] = a[2] * invLen, c3[1] = 0.0f, c3[2] = -a[0] * invLen;
+        } else {
+            const float invLen = 1.0f / std::sqrt(a[1] * a[1] + a[2] * a[2]);
+            c3[0] = 0.0f, c3[1] = a[2] * invLen, c3[2] = -a[1] * invLen;
+        }
+        dpdu[0] = c3[1] * a[2] - c3[2] * a[1];
+        dpdu[1] = c3[2] * a[0] - c3[0] * a[2];
+        dpdu[2] = c3[0] * a[1] - c3[1] * a[0];
+        return;
+    }
+    const float invDet = 1.0f / det;
+    for (int a = 0; a < 3; ++a) dpdu[a] = (u2[1] * d1[a] - u1[1] * d2[a]) * invDet;
+}
+// What pg_set_textures and pg_set_normal_maps share, rebuilt from what each was given (Ctx::host_mtex / host_mnmap,
+// tex_uv / nmap_uv): the per-triangle uv records, the triangle classes, mtex (all ~0 while only normal maps are
+// bound: the kernels take mtex != nullptr for "the textured class exists") and the mapped triangles' tangents.
+pg_status syncTexRows(Ctx *c) {
+    pg_status s;
+    if (!c->textured) c->mtex.release();
+    if (!c->nmapped) c->ttan.release();
+    if (!c->textured && !c->nmapped) {
+        if ((s = upload(c, c->tclass, c->base_tclass))) return s;
+        HIPC(c, hipStreamSynchronize(c->stream));
+        c->tuv.release();
+        return PG_OK;
+    }
+    const float *texcoords = !c->tex_uv.empty() ? c->tex_uv.data() : !c->nmap_uv.empty() ? c->nmap_uv.data() : nullptr;
+    const std::vector<uint32_t> none(c->num_mats, 0xFFFFFFFFu);
+    const std::vector<uint32_t> &mtex = c->textured ? c->host_mtex : none, &mnmap = c->nmapped ? c->host_mnmap : none;
+    // per BVH-order triangle: the vertices' texcoords (pg_layout.h PG_TRI_UV_F4), the textured class, the tangent
+    const uint32_t nt = c->num_tris;
+    std::vector<float> tuv((size_t)4 * PG_TRI_UV_F4 * nt, 0.0f), ttan(c->nmapped ? (size_t)4 * nt : 0, 0.0f);
+    std::vector<uint8_t> tclass = c->base_tclass;
+    for (uint32_t k = 0; k < nt; ++k) {
+        const float *rec = &c->host_shade[4 * PG_TRI_SHADE_STRIDE * (size_t)k];
+        uint32_t bits, orig;
+        std::memcpy(&bits, rec + 3, 4);
+        std::memcpy(&orig, rec + 11, 4);
+        float *o = &tuv[(size_t)4 * PG_TRI_UV_F4 * k];
+        if (texcoords) {
+            for (int v = 0; v < 3; ++v) {
+                const uint32_t vi = c->host_indices[3 * (size_t)orig + v];
+                o[2 * v] = texcoords[2 * (size_t)vi];
+                o[2 * v + 1] = texcoords[2 * (size_t)vi + 1];
+            }
+        } else {  // Intersection::uv without texcoords: (b.y, b.z)
+            o[2] = 1.0f;
+            o[5] = 1.0f;
+        }
+        const uint32_t m = bits & 0xFFFFu;
+        if (mtex[m] != 0xFFFFFFFFu || mnmap[m] != 0xFFFFFFFFu)
+            tclass[k] = (uint8_t)(PG_CLASS_TEXTURED | (tclass[k] & PG_TCLASS_EMITTER));
+        // unmapped triangles never read their row: p1 - p0, the frame they keep
+        if (c->nmapped) uvTangent(rec, rec + 4, rec + 8, texcoords && mnmap[m] != 0xFFFFFFFFu ? o : nullptr, &ttan[4 * (size_t)k]);
+    }
+    if ((s = upload(c, c->tuv, tuv)) || (s = upload(c, c->mtex, mtex)) || (s = upload(c, c->tclass, tclass))) return s;
+    if (c->nmapped && (s = upload(c, c->ttan, ttan))) return s;
+    HIPC(c, hipStreamSynchronize(c->stream));
+    return PG_OK;
+}
+// the untextured scene's materials back on the device, and the shared rows without the textures
 pg_status clearTextures(Ctx *c) {
     if (!c->textured) return PG_OK;
     c->textured = false;
     c->host_mats = c->base_mats;
+    c->host_mtex.clear();
+    c->tex_uv.clear();
     pg_status s;
-    if ((s = upload(c, c->mats, c->host_mats)) || (s = upload(c, c->tclass, c->base_tclass))) return s;
+    if ((s = upload(c, c->mats, c->host_mats)) || (s = syncTexRows(c))) return s;
     HIPC(c, hipStreamSynchronize(c->stream));
-    for (DevBuf *b : {&c->tuv, &c->tex, &c->mtex, &c->texels}) b->release();
+    for (DevBuf *b : {&c->tex, &c->texels}) b->release();
+    return PG_OK;
+}
+// the scene without normal maps (they change no material record)
+pg_status clearNormalMaps(Ctx *c) {
+    if (!c->nmapped) return PG_OK;
+    c->nmapped = false;
+    c->host_mnmap.clear();
+    c->nmap_uv.clear();
+    if (pg_status s = syncTexRows(c)) return s;
+    for (DevBuf *b : {&c->ntex, &c->mnmap, &c->ntexels}) b->release();
+    return PG_OK;
+}
+// both calls' texcoords describe the same mesh: equal where both pass them
+bool sameTexcoords(const std::vector<float> &other, const float *texcoords) {
+    if (!texcoords || other.empty()) return true;
+    for (size_t i = 0; i < other.size(); ++i)
+        if (other[i] != texcoords[i]) return false;
+    return true;
+}
+// the texel buffer of a texture set (each bitmap 256-B aligned) and the records pointing into it
+pg_status uploadTexels(Ctx *c, const pg_texture *textures, uint32_t n_textures, DevBuf &buf, std::vector<GTex> &gtex) {
+    std::vector<float> texels;
+    std::vector<size_t> at(n_textures, 0);
+    for (uint32_t i = 0; i < n_textures; ++i) {
+        if (textures[i].type != PG_TEXTURE_BITMAP) continue;
+        texels.resize((texels.size() + 63) & ~(size_t)63, 0.0f);
+        at[i] = texels.size();
+        std::vector<float> rows;
+        texelRows(textures[i], rows);
+        texels.insert(texels.end(), rows.begin(), rows.end());
+    }
+    if (pg_status s = upload(c, buf, texels)) return s;
+    for (uint32_t i = 0; i < n_textures; ++i)
+        if (textures[i].type == PG_TEXTURE_BITMAP) gtex[i].texels = buf.as<float>() + at[i];
     return PG_OK;
 }
 }  // namespace
@@ -922,20 +1039,11 @@ pg_status pg_set_textures(void *ctx, const pg_texture *textures, uint32_t n_text
     if (texcoords)
         for (size_t i = 0; i < (size_t)2 * c->num_vertices; ++i)
             if (!std::isfinite(texcoords[i])) return fail(c, PG_ERR_INVALID, "pg_set_textures: non-finite texcoord");
+    if (n_bindings && !sameTexcoords(c->nmap_uv, texcoords))
+        return fail(c, PG_ERR_INVALID, "pg_set_textures: texcoords differ from those of pg_set_normal_maps");
     if (pg_status s = clearTextures(c)) return s;
     if (n_bindings == 0) return PG_OK;
 
-    // texels: one buffer, each bitmap 256-B aligned
-    std::vector<float> texels;
-    std::vector<size_t> at(n_textures, 0);
-    for (uint32_t i = 0; i < n_textures; ++i) {
-        if (textures[i].type != PG_TEXTURE_BITMAP) continue;
-        texels.resize((texels.size() + 63) & ~(size_t)63, 0.0f);
-        at[i] = texels.size();
-        std::vector<float> rows;
-        texelRows(textures[i], rows);
-        texels.insert(texels.end(), rows.begin(), rows.end());
-    }
     // from here on a failure puts the untextured scene back (restoreBase): the context never holds half a texture set
     auto restoreBase = [&](pg_status why) {
         const std::string msg = c->err;
@@ -945,9 +1053,7 @@ pg_status pg_set_textures(void *ctx, const pg_texture *textures, uint32_t n_text
         return why;
     };
     pg_status s;
-    if ((s = upload(c, c->texels, texels))) return restoreBase(s);
-    for (uint32_t i = 0; i < n_textures; ++i)
-        if (textures[i].type == PG_TEXTURE_BITMAP) gtex[i].texels = c->texels.as<float>() + at[i];
+    if ((s = uploadTexels(c, textures, n_textures, c->texels, gtex))) return restoreBase(s);
     // the bound materials: specWeight from the texture's average (plastic.cpp:201-202, roughplastic.cpp:258-262) and
     // wbound from its per-channel maximum, an upper bound only (shadeOne computes the vertex's own)
     std::vector<GMat> mats = c->base_mats;
@@ -964,31 +1070,10 @@ pg_status pg_set_textures(void *ctx, const pg_texture *textures, uint32_t n_text
         for (int k = 0; k < 3; ++k) a[k] = gm.model == PG_BSDF_DIFFUSE ? mx[k] : mx[k] * 0.5f + gm.spec[k] * 0.5f;
         gm.wbound = std::max(std::max(a[0], a[1]), a[2]);
     }
-    // per BVH-order triangle: the vertices' texcoords (pg_layout.h PG_TRI_UV_F4), and the textured class
-    const uint32_t nt = c->num_tris;
-    std::vector<float> tuv((size_t)4 * PG_TRI_UV_F4 * nt, 0.0f);
-    std::vector<uint8_t> tclass = c->base_tclass;
-    for (uint32_t k = 0; k < nt; ++k) {
-        const float *rec = &c->host_shade[4 * PG_TRI_SHADE_STRIDE * (size_t)k];
-        uint32_t bits, orig;
-        std::memcpy(&bits, rec + 3, 4);
-        std::memcpy(&orig, rec + 11, 4);
-        float *o = &tuv[(size_t)4 * PG_TRI_UV_F4 * k];
-        if (texcoords) {
-            for (int v = 0; v < 3; ++v) {
-                const uint32_t vi = c->host_indices[3 * (size_t)orig + v];
-                o[2 * v] = texcoords[2 * (size_t)vi];
-                o[2 * v + 1] = texcoords[2 * (size_t)vi + 1];
-            }
-        } else {  // Intersection::uv without texcoords: (b.y, b.z)
-            o[2] = 1.0f;
-            o[5] = 1.0f;
-        }
-        if (mtex[bits & 0xFFFFu] != 0xFFFFFFFFu) tclass[k] = (uint8_t)(PG_CLASS_TEXTURED | (tclass[k] & PG_TCLASS_EMITTER));
-    }
-    if ((s = upload(c, c->tuv, tuv)) || (s = upload(c, c->tex, gtex)) || (s = upload(c, c->mtex, mtex)) ||
-        (s = upload(c, c->mats, mats)) || (s = upload(c, c->tclass, tclass)))
-        return restoreBase(s);
+    c->textured = true;  // syncTexRows reads the new set; restoreBase clears it again
+    c->host_mtex = mtex;
+    if (texcoords) c->tex_uv.assign(texcoords, texcoords + 2 * (size_t)c->num_vertices);
+    if ((s = upload(c, c->tex, gtex)) || (s = upload(c, c->mats, mats)) || (s = syncTexRows(c))) return restoreBase(s);
     if (hipStreamSynchronize(c->stream) != hipSuccess) return restoreBase(fail(c, PG_ERR_HIP, "pg_set_textures: upload failed"));
     c->host_mats = mats;
     c->textured = true;
@@ -1039,6 +1124,83 @@ pg_status pg_hit_uvs(void *ctx, const float *rays, uint64_t n, float *out) {
     pg_launch_hit_uvs(c->stream, sceneView(c), r.as<float>(), (uint32_t)n, o.as<float>(), ovf.as<uint32_t>());
     HIPC(c, hipGetLastError());
     HIPC(c, hipMemcpyAsync(out, o.p, n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    return PG_OK;
+}
+
+// ---- normal maps (pg_capi.h pg_set_normal_maps) ----------------------------------------------------------------------
+pg_status pg_set_normal_maps(void *ctx, const pg_texture *maps, uint32_t n_maps, const pg_texture_binding *bindings,
+                             uint32_t n_bindings, const float *texcoords) {
+    Ctx *c = (Ctx *)ctx;
+    if (!c) return fail(nullptr, PG_ERR_INVALID, "pg_set_normal_maps: null context");
+    if (c->cfg.integrator != PG_INTEGRATOR_PATH)
+        return fail(c, PG_ERR_INVALID, "pg_set_normal_maps: the volumetric integrator does not support normal maps");
+    if (!c->has_scene) return fail(c, PG_ERR_STATE, "pg_set_normal_maps: no scene uploaded");
+    if (c->scene_rendered) return fail(c, PG_ERR_STATE, "pg_set_normal_maps: a render pass has already run on this scene");
+    if ((n_maps && !maps) || (n_bindings && !bindings)) return fail(c, PG_ERR_INVALID, "pg_set_normal_maps: null argument");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    // validate everything before anything changes
+    std::vector<GTex> gtex(n_maps);
+    for (uint32_t i = 0; i < n_maps; ++i) {
+        std::string err;
+        if (!makeGTex(maps[i], gtex[i], err))
+            return fail(c, PG_ERR_INVALID, "pg_set_normal_maps: map " + std::to_string(i) + ": " + err);
+    }
+    std::vector<uint32_t> mnmap(c->num_mats, 0xFFFFFFFFu);
+    for (uint32_t b = 0; b < n_bindings; ++b) {
+        const pg_texture_binding &tb = bindings[b];
+        if (tb.material >= c->num_mats || tb.texture >= n_maps)
+            return fail(c, PG_ERR_INVALID, "pg_set_normal_maps: binding " + std::to_string(b) + ": index out of range");
+        const uint32_t model = c->base_mats[tb.material].model;
+        if (model != PG_BSDF_DIFFUSE && model != PG_BSDF_PLASTIC && model != PG_BSDF_ROUGHPLASTIC &&
+            model != PG_BSDF_CONDUCTOR && model != PG_BSDF_ROUGHCONDUCTOR)
+            return fail(c, PG_ERR_INVALID, "pg_set_normal_maps: binding " + std::to_string(b) +
+                                               ": the material's model (dielectric, roughdielectric or null) takes no normal map");
+        if (mnmap[tb.material] != 0xFFFFFFFFu)
+            return fail(c, PG_ERR_INVALID, "pg_set_normal_maps: material " + std::to_string(tb.material) + " is bound twice");
+        mnmap[tb.material] = tb.texture;
+    }
+    if (texcoords)
+        for (size_t i = 0; i < (size_t)2 * c->num_vertices; ++i)
+            if (!std::isfinite(texcoords[i])) return fail(c, PG_ERR_INVALID, "pg_set_normal_maps: non-finite texcoord");
+    if (n_bindings && !sameTexcoords(c->tex_uv, texcoords))
+        return fail(c, PG_ERR_INVALID, "pg_set_normal_maps: texcoords differ from those of pg_set_textures");
+    if (pg_status s = clearNormalMaps(c)) return s;
+    if (n_bindings == 0) return PG_OK;
+
+    // from here on a failure puts the scene without normal maps back, as pg_set_textures does for its set
+    auto restoreBase = [&](pg_status why) {
+        const std::string msg = c->err;
+        c->nmapped = true;
+        (void)clearNormalMaps(c);
+        c->err = msg;
+        return why;
+    };
+    pg_status s;
+    if ((s = uploadTexels(c, maps, n_maps, c->ntexels, gtex))) return restoreBase(s);
+    c->nmapped = true;
+    c->host_mnmap = mnmap;
+    if (texcoords) c->nmap_uv.assign(texcoords, texcoords + 2 * (size_t)c->num_vertices);
+    if ((s = upload(c, c->ntex, gtex)) || (s = upload(c, c->mnmap, mnmap)) || (s = syncTexRows(c))) return restoreBase(s);
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return restoreBase(fail(c, PG_ERR_HIP, "pg_set_normal_maps: upload failed"));
+    return PG_OK;
+}
+
+pg_status pg_hit_frames(void *ctx, const float *rays, uint64_t n, float *out) {
+    Ctx *c = (Ctx *)ctx;
+    if (!c || (!rays && n) || (!out && n)) return fail(c, PG_ERR_INVALID, "pg_hit_frames: null argument");
+    if (!c->has_scene) return fail(c, PG_ERR_STATE, "pg_hit_frames: no scene");
+    if (n > 0xFFFFFFFFull / 12) return fail(c, PG_ERR_INVALID, "pg_hit_frames: too many rays");
+    HIPC(c, hipSetDevice(c->cfg.device));
+    if (!n) return PG_OK;
+    DevBuf r, o, ovf;
+    HIPC(c, r.alloc(n * 32));
+    HIPC(c, o.alloc(n * 48));
+    HIPC(c, ovf.alloc(pg_stack_overflow_words(pg_trace_rays_threads(n)) * 4));
+    HIPC(c, hipMemcpyAsync(r.p, rays, n * 32, hipMemcpyHostToDevice, c->stream));
+    pg_launch_hit_frames(c->stream, sceneView(c), r.as<float>(), (uint32_t)n, o.as<float>(), ovf.as<uint32_t>());
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipMemcpyAsync(out, o.p, n * 48, hipMemcpyDeviceToHost, c->stream));
     HIPC(c, hipStreamSynchronize(c->stream));
     return PG_OK;
 }
@@ -1376,9 +1538,11 @@ pg_status pg_upload_scene(void *ctx, const pg_scene_desc *d) {
     c->host_tris = bvh.tris;
     c->host_shade = shade;
     // a new scene has no textures (pg_set_textures)
-    c->textured = false;
+    c->textured = c->nmapped = false;
     c->scene_rendered = false;
-    for (DevBuf *b : {&c->tuv, &c->tex, &c->mtex, &c->texels}) b->release();
+    for (DevBuf *b : {&c->tuv, &c->tex, &c->mtex, &c->texels, &c->ntex, &c->mnmap, &c->ntexels, &c->ttan}) b->release();
+    for (auto *v : {&c->host_mtex, &c->host_mnmap}) v->clear();
+    for (auto *v : {&c->tex_uv, &c->nmap_uv}) v->clear();
     c->base_tclass = tclass;
     c->host_indices.assign(d->indices, d->indices + 3 * (size_t)nt);
     c->num_vertices = d->num_vertices;

@@ -41,6 +41,11 @@ struct SceneDev {
     uint32_t *prb_counts;   // per BVH-order triangle: probes whose walk accepted it (recording passes; nullptr: not counted)
     uint32_t *prb_total;    // the probes, hit or miss, that prb_counts was taken from (one word)
     float prb[PG_PROBE_LIST_MAX][12];
+    // normal maps (pg_set_normal_maps; after prb so that no other member moves); all nullptr while none is bound.
+    // While one is bound mtex is allocated too (all ~0 without textures): mtex != nullptr selects the TEX kernels
+    const GTex *ntex;
+    const uint32_t *mnmap;  // per material: the normal map bound to it, ~0 = none
+    const float4 *ttan;     // per BVH-order triangle: (dpdu, 0), the UV tangent of a mapped material's triangle
 };
 
 // float4 per training vertex: (x, woPdf), (T after the vertex, packed canonical wo), (L snapshot, -),
@@ -328,6 +333,8 @@ void pg_launch_trace_rays(hipStream_t s, const SceneDev &sc, const float *rays, 
 void pg_launch_texture_query(hipStream_t s, const GTex *tex, const float *uv, uint32_t n, float *out);
 // closest hits' interpolated uv (pg_hit_uvs): n x 2, (0, 0) for a miss
 void pg_launch_hit_uvs(hipStream_t s, const SceneDev &sc, const float *rays, uint32_t n, float *out, uint32_t *ovf);
+// the BSDF frame of the closest hits (pg_hit_frames): n x 12 (n', s', t', wi'), zeros for a miss
+void pg_launch_hit_frames(hipStream_t s, const SceneDev &sc, const float *rays, uint32_t n, float *out, uint32_t *ovf);
 // unit-level blocker test (pg_blocker_test): out[i] = 1 where pg_ray_hits_blockers answers for ray i against sc.blk
 void pg_launch_blocker_test(hipStream_t s, const SceneDev &sc, const float *rays, uint32_t n, uint32_t *out);
 // unit-level occluder test (pg_occluder_test): out[2 i] = pg_ray_hits_occluders' answer for ray i against sc.prb,

@@ -559,7 +559,9 @@ extern "C" int pg_debug_watch_read(float *out, uint32_t max, uint32_t *n) {
 
 // TEX (the textured class, pg_layout.h PG_CLASS_TEXTURED): the vertex's material has a texture as its diffuse
 // reflectance.  The lookup replaces the register copy of GMat::diff and the albedo bound, and the BSDF code runs on
-// that copy unchanged; with TEX = false none of it is compiled.
+// that copy unchanged; with TEX = false none of it is compiled.  A material of that class may also carry a normal map
+// (pg_set_normal_maps): every BSDF call of the vertex then runs in the perturbed frame under normalmap.cpp's hemisphere
+// rule, and the side tests keep the unperturbed normal.
 // DELTA: delta emitters are set (pg_set_delta_emitters): sampleEmitter's point / spot / directional branches and the
 // discrete-measure rule of the NEE below; with DELTA = false none of it is compiled.
 template <int MODEL, bool CAN_GUIDE, bool ENV, bool TEX = false, bool DELTA = false>
@@ -671,6 +673,14 @@ __device__ __forceinline__ void shadeOne(const GParams &g, const SceneDev &sc, c
         if ((g.max_depth > 0 && (int)depth >= g.max_depth) ||
             (g.strict_normals && dot(rd, h.geoN) * h.wi.z >= 0))
             break;
+        // a normal-mapped material: from here on h.sh and h.wi are the perturbed frame and -d in it; h.shN stays
+        bool mapped = false;
+        if constexpr (TEX) {
+            mapped = nmapFrame(sc, tri, hv.z, hv.w, h.mat, h.shN, h.sh);
+            if (mapped) h.wi = h.sh.toLocal(-rd);
+        }
+        // normalmap.cpp:215,233,258,280: wo on opposite sides of the unperturbed and the perturbed tangent plane
+        auto wrongSide = [&](f3 woW, float woZ) { return TEX && mapped && dot(woW, h.shN) * woZ <= 0; };
         WSET3(18, L);
         const f3 refN = (M.type & (ETransmission | EBackSide)) == 0 ? h.shN : mk1(0.f);
         // glossy prior (pg_config.glossy_prior): r = BSDF::getGlossySamplingRate; r = 1 is not guided
@@ -705,8 +715,10 @@ __device__ __forceinline__ void shadeOne(const GParams &g, const SceneDev &sc, c
             f3 value = sampleEmitter<ENV, DELTA>(g, sc, h.p, refN, s0, s1, neeD, neeDist, emPdf, nullptr, &discrete);
             if (!isZero(value)) {
                 f3 woL = h.sh.toLocal(neeD);
-                f3 bsdfVal = bsdfEval<MODEL>(M, h.wi, woL);
-                if (!isZero(bsdfVal) && (!g.strict_normals || dot(h.geoN, neeD) * woL.z > 0)) {
+                f3 bsdfVal = wrongSide(neeD, woL.z) ? mk1(0.f) : bsdfEval<MODEL>(M, h.wi, woL);
+                // strict normals test bRec.wo, a direction of the unperturbed frame
+                const float woZ = TEX && mapped ? dot(neeD, h.shN) : woL.z;
+                if (!isZero(bsdfVal) && (!g.strict_normals || dot(h.geoN, neeD) * woZ > 0)) {
                     neeBp = bsdfPdf<MODEL>(M, h.wi, woL);
                     neeEmPdf = emPdf;
                     neeV = T * value * bsdfVal;
@@ -742,9 +754,11 @@ __device__ __forceinline__ void shadeOne(const GParams &g, const SceneDev &sc, c
             float bu = 0, bw = 0;
             if (!guide) {
                 weight = bsdfSample<MODEL>(M, h.wi, b0, b1, b2, bs);
+                if (!isZero(weight) && wrongSide(h.sh.toWorld(bs.wo), bs.wo.z)) weight = mk1(0.f);
                 woPdf = bs.pdf;
             } else if (rng1(key, sample, dimOf(depth, SLOT_GUIDE_CHOICE)) < alpha) {
                 weight = bsdfSample<MODEL>(M, h.wi, b0, b1, b2, bs);
+                if (!isZero(weight) && wrongSide(h.sh.toWorld(bs.wo), bs.wo.z)) weight = mk1(0.f);
                 if (isZero(weight)) {
                     ok = false;
                 } else {
@@ -767,8 +781,9 @@ __device__ __forceinline__ void shadeOne(const GParams &g, const SceneDev &sc, c
                 } else if (mode == 2) {
                     f3 dW = canonicalToDir(cu, cv);
                     f3 woL = h.sh.toLocal(dW);
-                    f3 f = bsdfEval<MODEL>(M, h.wi, woL);
-                    float bp = bsdfPdf<MODEL>(M, h.wi, woL);
+                    const bool wrong = wrongSide(dW, woL.z);
+                    f3 f = wrong ? mk1(0.f) : bsdfEval<MODEL>(M, h.wi, woL);
+                    float bp = wrong ? 0.0f : bsdfPdf<MODEL>(M, h.wi, woL);
                     woPdf = alpha * bp + (1 - alpha) * dPdf;
                     if (!(woPdf > 0) || isZero(f)) {
                         ok = false;
@@ -797,7 +812,8 @@ __device__ __forceinline__ void shadeOne(const GParams &g, const SceneDev &sc, c
         if (ok && !isZero(weight)) {
             if (bs.type != ENull) flags |= PF_SCATTERED;
             f3 wo = h.sh.toWorld(bs.wo);
-            if (!(g.strict_normals && dot(h.geoN, wo) * bs.wo.z <= 0)) {
+            const float woZ = TEX && mapped ? dot(wo, h.shN) : bs.wo.z;  // bRec.wo.z of the unperturbed frame
+            if (!(g.strict_normals && dot(h.geoN, wo) * woZ <= 0)) {
                 f3 Tn = T * weight;
                 // training vertex: (x, wo, woPdf, T after this bounce, L snapshot)
                 if (g.record && !(bs.type & EDelta) && nv < (uint32_t)g.max_vertices) {
@@ -944,7 +960,7 @@ __global__ __launch_bounds__(SHADE_BLOCK) __attribute__((amdgpu_waves_per_eu(PG_
     else if (b < r.end[4]) shadeBlock<PG_BSDF_ROUGHPLASTIC, true, false, false, DELTA>(g, sc, sd, p, in.q[4], out, shq, pq, b - r.end[3]);
     else if (!TEX || b < r.end[5]) shadeBlock<-1, false, false, false, DELTA>(g, sc, sd, p, in.q[5], out, shq, pq, b - r.end[4]);
     else if constexpr (TEX)
-        shadeBlock<PG_MODELS_DIFFUSE_SLOT, true, false, true, DELTA>(g, sc, sd, p, in.q[6], out, shq, pq, b - r.end[5]);
+        shadeBlock<PG_MODELS_TEXTURED, true, false, true, DELTA>(g, sc, sd, p, in.q[6], out, shq, pq, b - r.end[5]);
 }
 
 // ---- counting sort of a queue's shards by ray order key (PG_RAY_SORT): the next closest-hit launch
@@ -1041,7 +1057,7 @@ __device__ __forceinline__ void tailShade(const GParams &g, const SceneDev &sc, 
     // the textured class: only scenes with textures bound have such triangles, and they run k_tail<.., TEX = true>
     if constexpr (TEX) {
         if ((sc.tclass[tri] & PG_TCLASS_MASK) == PG_CLASS_TEXTURED) {
-            shadeOne<PG_MODELS_DIFFUSE_SLOT, true, ENV, true, DELTA>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, probe, rk, blocked);
+            shadeOne<PG_MODELS_TEXTURED, true, ENV, true, DELTA>(g, sc, sd, p, slot, sc.mats, false, alive, shadow, probe, rk, blocked);
             return;
         }
     }
@@ -1648,6 +1664,33 @@ __global__ __launch_bounds__(TRACE_BLOCK) void k_hit_uvs(SceneDev sc, const floa
     out[2 * (size_t)i] = tu;
     out[2 * (size_t)i + 1] = tv;
 }
+// pg_hit_frames: the frame the closest hit's BSDF calls run in and -d in it, as shadeOne forms them (fetchHit, then
+// nmapFrame where the material carries a normal map); rows as k_trace_rays', 12 floats per ray, zeros for a miss
+__global__ __launch_bounds__(TRACE_BLOCK) void k_hit_frames(SceneDev sc, const float *__restrict__ rays, uint32_t n,
+                                                            float *__restrict__ out, uint32_t *ovf) {
+    __shared__ uint32_t stack[2 * WIDE_LDS_STACK * TRACE_BLOCK];  // >= LDS_STACK words per thread
+    const TStack stk = threadStack(stack, ovf);
+    const uint32_t i = blockIdx.x * TRACE_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const float *r = rays + 8 * (size_t)i;
+    const f3 o = mk(r[0], r[1], r[2]), d = mk(r[4], r[5], r[6]);
+    float tmax = r[7], u = 0, v = 0;
+    uint32_t tri = 0xFFFFFFFFu;
+    float *f = out + 12 * (size_t)i;
+    if (!traverse<false>(sc.nodes, sc.tris, o, d, r[3], tmax, tri, u, v, stk)) {
+        for (int k = 0; k < 12; ++k) f[k] = 0.0f;
+        return;
+    }
+    Hit h;
+    fetchHit(sc, tri, u, v, d, h);
+    if (nmapFrame(sc, tri, u, v, h.mat, h.shN, h.sh)) h.wi = h.sh.toLocal(-d);
+    const f3 rows[4] = {h.sh.n, h.sh.s, h.sh.t, h.wi};
+    for (int k = 0; k < 4; ++k) {
+        f[3 * k] = rows[k].x;
+        f[3 * k + 1] = rows[k].y;
+        f[3 * k + 2] = rows[k].z;
+    }
+}
 
 // pg_blocker_test: the shader's blocker test on given rays (rows as k_trace_rays')
 __global__ __launch_bounds__(256) void k_blocker_test(SceneDev sc, const float *__restrict__ rays, uint32_t n,
@@ -1837,7 +1880,7 @@ static void launchShade(hipStream_t s, int cls, dim3 grid, const GParams &g, con
             hipLaunchKernelGGL((k_shade<PG_BSDF_ROUGHPLASTIC, true, ENV, false, DELTA>), grid, block, 0, s, g, sc, sd, p, in, out, shq, pq);
             break;
         case PG_CLASS_TEXTURED:  // a textured diffuse reflectance (diffuse, plastic, roughplastic at run time)
-            hipLaunchKernelGGL((k_shade<PG_MODELS_DIFFUSE_SLOT, true, ENV, true, DELTA>), grid, block, 0, s, g, sc, sd, p, in, out, shq, pq);
+            hipLaunchKernelGGL((k_shade<PG_MODELS_TEXTURED, true, ENV, true, DELTA>), grid, block, 0, s, g, sc, sd, p, in, out, shq, pq);
             break;
         default:  // delta lobes: conductor, dielectric (runtime switch, never guided)
             hipLaunchKernelGGL((k_shade<-1, false, ENV, false, DELTA>), grid, block, 0, s, g, sc, sd, p, in, out, shq, pq);
@@ -2091,6 +2134,9 @@ void pg_launch_texture_query(hipStream_t s, const GTex *tex, const float *uv, ui
 }
 void pg_launch_hit_uvs(hipStream_t s, const SceneDev &sc, const float *rays, uint32_t n, float *out, uint32_t *ovf) {
     if (n) hipLaunchKernelGGL(k_hit_uvs, dim3(blocks(n, TRACE_BLOCK)), dim3(TRACE_BLOCK), 0, s, sc, rays, n, out, ovf);
+}
+void pg_launch_hit_frames(hipStream_t s, const SceneDev &sc, const float *rays, uint32_t n, float *out, uint32_t *ovf) {
+    if (n) hipLaunchKernelGGL(k_hit_frames, dim3(blocks(n, TRACE_BLOCK)), dim3(TRACE_BLOCK), 0, s, sc, rays, n, out, ovf);
 }
 void pg_launch_blocker_test(hipStream_t s, const SceneDev &sc, const float *rays, uint32_t n, uint32_t *out) {
     if (!n) return;

@@ -689,6 +689,25 @@ __device__ __forceinline__ f3 texEval(const GTex &t, float tu, float tv) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Normal maps (pg_capi.h pg_set_normal_maps): NormalMap::getFrame (normalmap.cpp:141-158) on the base frame
+// computeShadingFrame(shN, dpdu) with the triangle's UV tangent (SceneDev::ttan, TriMesh::computeUVTangents).
+// Returns whether the hit's material carries a map; then `sh` is (s', t', n'), else it is left alone.
+__device__ __forceinline__ bool nmapFrame(const SceneDev &sc, uint32_t tri, float u, float v, uint32_t mat, f3 shN,
+                                          Frame &sh) {
+    if (!sc.mnmap) return false;
+    const uint32_t ni = sc.mnmap[mat];
+    if (ni == 0xFFFFFFFFu) return false;
+    float tu, tv;
+    hitUV(sc, tri, u, v, tu, tv);
+    const f3 c = texEval(sc.ntex[ni], tu, tv);
+    const f3 dpdu = xyz(sc.ttan[tri]);
+    const Frame base = shadingFrame(shN, dpdu);
+    const f3 nl = mk(2 * c.x - 1, 2 * c.y - 1, 2 * c.z - 1);
+    sh = shadingFrame(normalize(base.toWorld(nl)), dpdu);
+    return true;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Environment emitter (src/emitters/envmap.cpp).  Texel lookups follow TMIPMap::evalTexel at level 0
 // (mipmap.h:503-563: repeat in x, clamp in y); the summation orders of evalBilinear (mipmap.h:575-596)
 // and internalSampleDirection / internalPdfDirection (envmap.cpp:567-633) are kept as written.

@@ -131,6 +131,8 @@ class Device:
         self._chk(self.lib.pg_upload_scene(self.h, C.byref(scene.desc())))
         if getattr(scene, "texture_bindings", None):  # pg_upload_scene cleared any textures of an earlier scene
             self.set_textures(scene.textures, scene.texture_bindings, scene.texcoords)
+        if getattr(scene, "normal_map_bindings", None):
+            self.set_normal_maps(scene.normal_maps, scene.normal_map_bindings, scene.texcoords)
         if getattr(scene, "lens", None):  # pg_upload_scene turned the lens off: its camera is a pinhole
             self.set_lens(*scene.lens)
         if getattr(scene, "delta_emitters", None):  # pg_upload_scene cleared any delta emitters of an earlier scene
@@ -215,6 +217,22 @@ class Device:
         if uv is not None and uv.shape != (self.scene.desc().num_vertices, 2):
             raise ValueError("texcoords: one (u, v) per vertex of the uploaded scene")
         self._chk(self.lib.pg_set_textures(self.h, tex, len(textures), bind, len(bindings), _p(uv) if uv is not None else None))
+
+    def set_normal_maps(self, maps, bindings, texcoords=None):
+        """pg_set_normal_maps: pg_texture records, (material, map) pairs and the texcoords, as set_textures."""
+        tex = (capi.pg_texture * max(1, len(maps)))(*maps)
+        bind = (capi.pg_texture_binding * max(1, len(bindings)))(*[capi.pg_texture_binding(m, t) for m, t in bindings])
+        uv = None if texcoords is None else np.ascontiguousarray(texcoords, np.float32)
+        if uv is not None and uv.shape != (self.scene.desc().num_vertices, 2):
+            raise ValueError("texcoords: one (u, v) per vertex of the uploaded scene")
+        self._chk(self.lib.pg_set_normal_maps(self.h, tex, len(maps), bind, len(bindings), _p(uv) if uv is not None else None))
+
+    def hit_frames(self, rays):
+        """pg_hit_frames: (n, 12) = (n', s', t', wi') of each ray's closest hit, the frame its BSDF calls run in."""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        out = np.zeros((len(rays), 12), np.float32)
+        self._chk(self.lib.pg_hit_frames(self.h, _p(rays), len(rays), _p(out)))
+        return out
 
     def texture_query(self, texture, uv):
         """pg_texture_query: the device lookup of one pg_texture at raw uv (n, 2) -> (n, 3)."""

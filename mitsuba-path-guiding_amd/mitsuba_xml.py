@@ -18,7 +18,8 @@ adapter's flatten() produces from Scene::getShapes()/getBSDFs() (INTEGRATION.md)
                     sampler sampleCount; film width / height and rfilter (box, tent, gaussian: recorded as Scene.rfilter)
   bsdf              diffuse, conductor, roughconductor (material Cu / Al / Au / none, or eta + k),
                     dielectric, roughdielectric, plastic, roughplastic (intIOR / extIOR by value or
-                    by name: src/bsdfs/ior.h), twosided, null; distribution beckmann / ggx
+                    by name: src/bsdfs/ior.h), twosided, null; distribution beckmann / ggx;
+                    normalmap as the outermost adapter (one nested bsdf, one bitmap with an explicit gamma)
   texture           bitmap (.npy / .pfm / .exr linear; 8-bit PNG / JPEG with the sRGB curve or 'gamma'; filterType
                     nearest / bilinear, ewa and trilinear as bilinear with a warning; wrapMode[U|V]) and
                     checkerboard, with uscale / vscale / uvscale / uoffset / voffset, as diffuse.reflectance or
@@ -126,6 +127,7 @@ class _Loader:
         self.sc.rfilter = ("gaussian", 0.5)
         self.mat_index = {}  # id(pg_material) -> scene material index
         self.tex_index = {}  # id(pg_texture) -> scene texture index
+        self.nmap_index = {}  # id(pg_texture) -> scene normal-map index
 
     # -- helpers
     def attr(self, el, name, default=None):
@@ -223,6 +225,7 @@ class _Loader:
                     raise NotImplementedError(f"<texture type=\"bitmap\">: wrapMode '{w}'")
             rgb = read_texture_image(self.path(P["filename"]), P.get("gamma"))
             t = scenes.make_texture("bitmap", rgb, filter=filt, wrap=wu, wrap_v=wv, **kw)
+            t._has_gamma = "gamma" in P
         else:
             raise NotImplementedError(f"<texture type=\"{typ}\"> (bitmap and checkerboard are supported)")
         if el.get("id"):
@@ -235,6 +238,8 @@ class _Loader:
         P = self.props(el)
         nested = [c for c in el if c.tag == "bsdf" or (c.tag == "ref" and
                                                        not isinstance(self.ids.get(c.get("id")), capi.pg_texture))]
+        if typ == "normalmap":
+            return self.normalmap(el, nested)
         # a texture as the diffuse reflectance of diffuse / plastic / roughplastic; any other textured parameter raises
         slot = {"diffuse": "reflectance", "plastic": "diffuseReflectance", "roughplastic": "diffuseReflectance"}.get(typ)
         tex = None
@@ -256,6 +261,32 @@ class _Loader:
             m._texture = tex
             return m
         return self._bsdf(typ, P, nested)
+
+    def normalmap(self, el, nested):
+        """<bsdf type="normalmap"> (src/bsdfs/normalmap.cpp): one nested bsdf and one bitmap texture; the material
+        comes back with the map as `_normalmap` (material_index binds it)."""
+        maps = [c for c in el if c.tag == "texture" or (c.tag == "ref" and isinstance(self.ids.get(c.get("id")), capi.pg_texture))]
+        if len(nested) != 1:
+            raise ValueError("normalmap needs one nested bsdf")
+        if len(maps) != 1:
+            raise ValueError("normalmap needs one normal map texture")
+        t = self.ids[maps[0].get("id")] if maps[0].tag == "ref" else self.texture(maps[0])
+        if t.type != capi.PG_TEXTURE_BITMAP:
+            raise NotImplementedError("<bsdf type=\"normalmap\">: only a bitmap texture is supported as the normal map")
+        if not getattr(t, "_has_gamma", False):  # normalmap.cpp:131-134
+            raise ValueError("<bsdf type=\"normalmap\">: the bitmap needs an explicit 'gamma' (in most cases "
+                             "<float name=\"gamma\" value=\"1.0\"/>)")
+        m = self.child_bsdf(nested[0])
+        if getattr(m, "_normalmap", None) is not None:
+            raise NotImplementedError("<bsdf type=\"normalmap\"> nested in another normalmap")
+        if m.type not in scenes.NORMAL_MAPPED_MODELS:
+            raise NotImplementedError("<bsdf type=\"normalmap\">: a dielectric, roughdielectric or null nested bsdf is not "
+                                      "supported (diffuse, plastic, roughplastic, conductor, roughconductor are)")
+        m2 = capi.pg_material.from_buffer_copy(m)
+        if getattr(m, "_texture", None) is not None:
+            m2._texture = m._texture
+        m2._normalmap = t
+        return m2
 
     def _bsdf(self, typ, P, nested):
 
@@ -279,6 +310,10 @@ class _Loader:
             if not nested:
                 raise ValueError("twosided needs a nested bsdf")
             m = self.child_bsdf(nested[0])
+            if getattr(m, "_normalmap", None) is not None:
+                raise NotImplementedError("twosided{normalmap{...}} mirrors the perturbed frame about the unperturbed "
+                                          "tangent plane on back-side hits, which the GPU path cannot express; write "
+                                          "normalmap{twosided{...}} (the flip then acts in the perturbed frame)")
             m2 = capi.pg_material.from_buffer_copy(m)
             m2.flags |= capi.PG_MAT_TWOSIDED
             if getattr(m, "_texture", None) is not None:
@@ -346,6 +381,12 @@ class _Loader:
                     self.tex_index[id(tex)] = len(self.sc.textures)
                     self.sc.textures.append(tex)
                 self.sc.bind_texture(self.mat_index[k], self.tex_index[id(tex)])
+            nmap = getattr(m, "_normalmap", None)
+            if nmap is not None:
+                if id(nmap) not in self.nmap_index:
+                    self.nmap_index[id(nmap)] = len(self.sc.normal_maps)
+                    self.sc.normal_maps.append(nmap)
+                self.sc.bind_normal_map(self.mat_index[k], self.nmap_index[id(nmap)])
         return self.mat_index[k]
 
     # -- meshes
@@ -1065,8 +1106,8 @@ _FILTER_NAMES = {v: k for k, v in scenes._TEX_FILTERS.items()}
 _WRAP_NAMES = {v: k for k, v in scenes._TEX_WRAPS.items()}
 
 
-def _texture_xml(t, name, fn):
-    """<texture> element of a pg_texture; fn: the file its texels were written to (bitmap)"""
+def _texture_xml(t, name, fn, extra=""):
+    """<texture> element of a pg_texture; fn: the file its texels were written to (bitmap); extra: further children"""
     f32 = lambda x: float(np.float32(x))
     xf = "".join(f'<float name="{k}" value="{f32(getattr(t, k))!r}"/>' for k in ("uscale", "vscale", "uoffset", "voffset"))
     if t.type == capi.PG_TEXTURE_CHECKERBOARD:
@@ -1075,10 +1116,10 @@ def _texture_xml(t, name, fn):
     return (f'<texture type="bitmap" name="{name}"><string name="filename" value="{fn}"/>'
             f'<string name="filterType" value="{_FILTER_NAMES[t.filter]}"/>'
             f'<string name="wrapModeU" value="{_WRAP_NAMES[t.wrap_u]}"/>'
-            f'<string name="wrapModeV" value="{_WRAP_NAMES[t.wrap_v]}"/>{xf}</texture>')
+            f'<string name="wrapModeV" value="{_WRAP_NAMES[t.wrap_v]}"/>{xf}{extra}</texture>')
 
 
-def _bsdf_xml(m, tex=None):
+def _bsdf_xml(m, tex=None, nmap=None):
     kind = _KIND[m.type]
     body = []
     f32 = lambda x: float(np.float32(x))
@@ -1113,6 +1154,8 @@ def _bsdf_xml(m, tex=None):
     inner = f'<bsdf type="{kind}">' + "".join(body) + "</bsdf>"
     if m.flags & capi.PG_MAT_TWOSIDED:
         inner = f'<bsdf type="twosided">{inner}</bsdf>'
+    if nmap is not None:  # the outermost adapter
+        inner = f'<bsdf type="normalmap">{nmap}{inner}</bsdf>'
     return inner
 
 
@@ -1184,6 +1227,15 @@ def save(scene, path, spp=64, integrator="path"):
             with open(os.path.join(d, tex_files[ti]), "wb") as f:
                 f.write(b"PF\n%d %d\n-1.0\n" % (img.shape[1], img.shape[0]))
                 f.write(img.tobytes())
+    nbound = dict(getattr(sc, "normal_map_bindings", []))
+    nmap_files = {}
+    for ti, t in enumerate(getattr(sc, "normal_maps", [])):
+        if ti in nbound.values():
+            nmap_files[ti] = f"{stem}_normalmap{ti}.pfm"
+            img = np.ascontiguousarray(t._rgb[::-1], "<f4")
+            with open(os.path.join(d, nmap_files[ti]), "wb") as f:
+                f.write(b"PF\n%d %d\n-1.0\n" % (img.shape[1], img.shape[0]))
+                f.write(img.tobytes())
     for si, sh in enumerate(sc.shapes):
         F = I[sh.tri_begin:sh.tri_begin + sh.tri_count].astype(np.int64)
         used = np.unique(F)
@@ -1212,11 +1264,15 @@ def save(scene, path, spp=64, integrator="path"):
             m = sc.materials[sh.material]
             slot = "reflectance" if m.type == capi.PG_BSDF_DIFFUSE else "diffuseReflectance"
             tex = _texture_xml(sc.textures[bound[sh.material]], slot, tex_files.get(bound[sh.material]))
+        nmap = None
+        if sh.material in nbound:  # the PFM is linear; the reference wants the gamma spelled out (normalmap.cpp:131)
+            nmap = _texture_xml(sc.normal_maps[nbound[sh.material]], "normals", nmap_files[nbound[sh.material]],
+                                '<float name="gamma" value="1"/>')
         flip = '<boolean name="flipTexCoords" value="false"/>' if UV is not None else ""
         med = "".join(f'<ref name="{side}" id="{homog[m]}"/>'
                       for side, m in (("interior", sh.interior_medium), ("exterior", sh.exterior_medium)) if m in homog)
         out.append(f'<shape type="obj"><string name="filename" value="{fn}"/>{flip}'
-                   f'{_bsdf_xml(sc.materials[sh.material], tex)}{em}{med}</shape>')
+                   f'{_bsdf_xml(sc.materials[sh.material], tex, nmap)}{em}{med}</shape>')
     if sc.envmap is not None:
         fn = f"{stem}_envmap.pfm"
         img = np.ascontiguousarray(sc._env_rgb[::-1], "<f4")

@@ -98,6 +98,9 @@ class Scene:
         self._uv = []
         self.textures = []
         self.texture_bindings = []
+        # normal maps (pg_set_normal_maps): pg_texture records (bitmaps), (material, map)
+        self.normal_maps = []
+        self.normal_map_bindings = []
         # thin lens (pg_set_lens): (aperture radius, focus distance), or None: the pinhole of `camera`
         self.lens = None
         # delta emitters (pg_set_delta_emitters): pg_delta_emitter records, picked after the area emitters
@@ -220,6 +223,25 @@ class Scene:
     def bind_texture(self, material, texture):
         """The diffuse reflectance of `material` (diffuse, plastic, roughplastic) is `texture`."""
         self.texture_bindings.append((int(material), int(texture)))
+
+    def add_normal_map(self, rgb, filter="bilinear", wrap="repeat", wrap_v=None, uscale=1.0, vscale=1.0, uoffset=0.0,
+                       voffset=0.0):
+        """A normal map for bind_normal_map: a bitmap as add_texture's, `rgb` (height, width, 3) linear in [0, 1]; a
+        texel c is the tangent-space normal 2 c - 1 (normalmap.cpp), so (0.5, 0.5, 1) leaves the frame alone."""
+        self.normal_maps.append(make_texture("bitmap", rgb, filter, wrap, wrap_v, uscale, vscale, uoffset, voffset))
+        return len(self.normal_maps) - 1
+
+    def bind_normal_map(self, material, normal_map):
+        """`material` (diffuse, plastic, roughplastic, conductor, roughconductor; twosided or not) is shaded in the
+        frame `normal_map` perturbs: normalmap{ [twosided{] bsdf [}] }."""
+        material, normal_map = int(material), int(normal_map)
+        if not 0 <= material < len(self.materials) or not 0 <= normal_map < len(self.normal_maps):
+            raise ValueError("bind_normal_map: index out of range")
+        if self.materials[material].type not in NORMAL_MAPPED_MODELS:
+            raise ValueError("bind_normal_map: dielectric, roughdielectric and null materials take no normal map")
+        if any(m == material for m, _ in self.normal_map_bindings):
+            raise ValueError(f"bind_normal_map: material {material} is bound twice")
+        self.normal_map_bindings.append((material, normal_map))
 
     @property
     def texcoords(self):
@@ -368,6 +390,8 @@ def directional_light(direction, irradiance):
     return e
 
 
+NORMAL_MAPPED_MODELS = (capi.PG_BSDF_DIFFUSE, capi.PG_BSDF_PLASTIC, capi.PG_BSDF_ROUGHPLASTIC, capi.PG_BSDF_CONDUCTOR,
+                        capi.PG_BSDF_ROUGHCONDUCTOR)
 _TEX_FILTERS = {"nearest": capi.PG_TEXFILTER_NEAREST, "bilinear": capi.PG_TEXFILTER_BILINEAR}
 _TEX_WRAPS = {"repeat": capi.PG_TEXWRAP_REPEAT, "clamp": capi.PG_TEXWRAP_CLAMP, "mirror": capi.PG_TEXWRAP_MIRROR,
               "zero": capi.PG_TEXWRAP_ZERO, "one": capi.PG_TEXWRAP_ONE}
